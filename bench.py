@@ -21,6 +21,13 @@ rounds (~7 in a CPU fp32 calibration) and the time-to-target half of the metric 
     python bench.py --gpus 1 --steps 20 --warmup 3
     torchrun --nproc-per-node 8 bench.py --gpus 8 --steps 20 --warmup 3
 
+A plain run sets up, warms up, times exactly ``--steps`` rounds and prints the result line
+(``ms_per_step``: milliseconds per timed round); the time to the target accuracy and the stderr
+diagnostics are read off those same rounds. ``--dump-outputs DIR`` also writes what the last round
+left behind (every local peer's model, the accuracy per round) as ``DIR/<name>.npy``: data, initial
+weights and shuffle keys are seeded, so two builds can be compared output for output. ``--full`` is
+where measurements that need runs of their own belong; this benchmark has none yet.
+
 Rank 0 prints ONE JSON line. Timing: barrier + device synchronize on both sides of exactly K rounds
 (inside the round-end hook that every rank's gang leader runs after aggregation), MAX over ranks.
 """
@@ -68,7 +75,33 @@ def parse() -> argparse.Namespace:
                          "auto = ranks under torchrun, mesh for one process started with --gpus N")
     ap.add_argument("--mesh-virtual", action="store_true",
                     help="rehearsal: N mesh ranks on the visible device(s) with host-side collectives (n_gpus reports the physical count)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed rounds write what the last round left with its callers as DIR/<name>.npy: every local peer's "
+                         "model parameters (float32) and the local peers' mean test accuracy per round (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements that take runs of their own. The headline run has none: the time to the target "
+                         "accuracy and the stderr diagnostics come out of the timed rounds themselves, so today this adds nothing")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory: str, arrays: dict) -> None:
+    """Write ``arrays`` (name -> array) as ``directory/<name>.npy`` in float32 (float64 stays), at most
+    DUMP_LIMIT_BYTES in all: an array over its equal share of the limit is cut to a fixed, seeded
+    sample of its flattened elements (same indices for the same shape in every run)."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > share:
+            keep = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[keep]
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def _engine_label(nodes, eager: bool) -> str:
@@ -234,6 +267,10 @@ def main() -> None:
         dev_sync()
         marks["t0"] = time.perf_counter()
     wait_to_finish(nodes, timeout=3600)
+    if args.dump_outputs:  # (after the clock stopped) let the last rounds' asynchronous evaluations land
+        deadline = time.perf_counter() + 10.0
+        while time.perf_counter() < deadline and any(len(landed.get(r, ())) < len(nodes) for r in range(total_rounds)):
+            time.sleep(0.005)
     t0, t1 = marks.get("t0"), marks.get("t1")
     elapsed = (t1 - t0) if (t0 is not None and t1 is not None) else float("nan")
     # max over the (live) ranks
@@ -280,6 +317,16 @@ def main() -> None:
     eng = getattr(nodes[0].learner, "_engine", None)
     if eng is not None and hasattr(eng.group, "graph_launch_stats"):
         print(f"[bench] rank {rank} epoch graph launches: {eng.group.graph_launch_stats()}", file=sys.stderr, flush=True)
+    if args.dump_outputs:
+        # what the last timed round left with its callers: each local peer's model as the Node API
+        # hands it out (the FedAvg result of that round), and the accuracy the rounds logged
+        dev_sync()
+        arrays = {f"peer{g:02d}_params": np.concatenate([np.asarray(p, dtype=np.float32).reshape(-1) for p in n.learner.get_model().get_parameters()])
+                  for g, n in zip(gids, nodes)}
+        if rank == 0:
+            # entry r: the model after round r - 1, evaluated at the start of round r (NaN: not landed)
+            arrays["test_acc_by_round"] = np.array([mean_acc.get(r, np.nan) for r in range(total_rounds)], dtype=np.float64)
+        dump_outputs(args.dump_outputs, arrays)
     for n in nodes:
         n.stop()
 

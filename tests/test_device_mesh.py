@@ -191,16 +191,28 @@ def test_bench_refuses_missing_gpus():
     assert "GPU" in (r.stderr + r.stdout)
 
 
-def test_bench_virtual_mesh_cpu():
-    """``--mesh-virtual``: 4 mesh ranks on the CPU run the mesh path and report 0 physical GPUs."""
+def test_bench_virtual_mesh_cpu(tmp_path):
+    """``--mesh-virtual``: 4 mesh ranks on the CPU run the mesh path and report 0 physical GPUs.
+    ``--dump-outputs``: the 8 peers' models after the last round (float32, equal: FedAvg over all of
+    them) and the accuracy per round (float64) are written as ``.npy``."""
     import json
 
+    import numpy as np
+
+    dump = tmp_path / "out"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--mesh-virtual", "--steps", "2", "--warmup", "1", "--n-train", "2000",
-                        "--n-test", "400"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--n-test", "400", "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads(r.stdout.strip().splitlines()[-1])
     assert out["n_gpus"] == 0 and out["config"]["peers_per_gpu"] == 2
     assert "mesh" in out["config"]["collective"]
+    assert out["steps"] == 2 and out["ms_per_step"] > 0
+    assert sorted(p.name for p in dump.iterdir()) == [f"peer{g:02d}_params.npy" for g in range(8)] + ["test_acc_by_round.npy"]
+    params = [np.load(dump / f"peer{g:02d}_params.npy") for g in range(8)]
+    assert all(p.dtype == np.float32 and p.shape == (784 * 256 + 256 + 256 * 128 + 128 + 128 * 10 + 10,) for p in params)
+    assert np.isfinite(params[0]).all() and all(np.allclose(p, params[0], atol=1e-5) for p in params[1:])
+    acc = np.load(dump / "test_acc_by_round.npy")
+    assert acc.dtype == np.float64 and acc.shape == (3,) and np.isfinite(acc).all()
 
 
 def test_bench_torchrun_mesh_parks_other_ranks_cpu():

@@ -3,6 +3,7 @@
 import os
 import shutil
 import subprocess
+import tempfile
 import time
 
 import pytest
@@ -37,9 +38,23 @@ def test_proto_roundtrip():
     assert from_proto(to_proto(w)) == w
 
 
+@pytest.fixture
+def sock_dir(tmp_path):
+    """A directory for Unix sockets: ``sun_path`` holds at most 107 characters, which pytest's
+    ``tmp_path`` can exceed under a deep temporary root, so a short one is made when it would."""
+    if len(f"{tmp_path}/n0.sock") <= 100:
+        yield str(tmp_path)
+        return
+    d = tempfile.mkdtemp(prefix="g", dir="/tmp")
+    try:
+        yield d
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+
+
 @pytest.mark.parametrize("unix", [False, True])
-def test_grpc_messages_and_weights(unix, tmp_path):
-    addrs = [f"unix://{tmp_path}/n{i}.sock" for i in range(2)] if unix else ["127.0.0.1", "127.0.0.1"]
+def test_grpc_messages_and_weights(unix, sock_dir):
+    addrs = [f"unix://{sock_dir}/n{i}.sock" for i in range(2)] if unix else ["127.0.0.1", "127.0.0.1"]
     a, b = GrpcCommunicationProtocol(addrs[0]), GrpcCommunicationProtocol(addrs[1])
     rec = Rec()
     b.add_command(rec)
