@@ -29,6 +29,7 @@ __device__ __forceinline__ uint4 pack8(const float* f) {
 // lightning_learner.py:110-114). stop is host-pinned memory the host writes while the epoch runs;
 // a peer whose stop word equals its current fit id gets an empty batch from this step on, so every
 // later kernel of the step (optimizer included: it skips peers with nb = 0) leaves it alone.
+// Contract: out rows at or beyond the valid count are zero; labels there are not written.
 __global__ void k_input_prep(const uint8_t* const* xs, const int64_t* const* ys, const int* n_samples, const int* perm, int64_t perm_ps,
                              int offset, int B, int H, int W, int C, int Cp, float scale, bf16* out, int64_t out_ps, int* labels, int* nb,
                              const int* stop, const int* fit_id) {
@@ -470,6 +471,7 @@ __global__ void k_maxpool2_fwd(const bf16* x, int64_t x_ps, const int* nb, int H
 }
 
 // gradient to the first maximal element of each window (torch semantics)
+// Contract: with odd H / W the last row / column belongs to no window and is never written (the caller keeps it zero).
 __global__ void k_maxpool2_bwd(const bf16* x, int64_t x_ps, const bf16* dy, int64_t dy_ps, const int* nb, int H, int W, int Cp, bf16* dx, int64_t dx_ps) {
   const int peer = blockIdx.y;
   const int Ho = H / 2, Wo = W / 2, cpp = Cp / 8;
