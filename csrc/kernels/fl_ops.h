@@ -38,6 +38,18 @@ struct RowW {
 };
 // out rows 0..P-1 <- per-coordinate median of rows 0..K-1 (outputs may alias inputs)
 void fl_coordinate_median(const OutPtrs& outs, int P, const RowPtrs& rows, int K, int64_t n, hipStream_t s);
+// out rows 0..P-1 <- per-coordinate mean of the sorted values v[trim .. K-trim) of rows 0..K-1
+// (0 <= 2*trim < K; outputs may alias inputs)
+void fl_trimmed_mean(const OutPtrs& outs, int P, const RowPtrs& rows, int K, int trim, int64_t n, hipStream_t s);
+// (Multi-)Krum. fl_krum_grid: blocks of the distance launch, a function of n and K only (work holds
+// grid * K(K-1)/2 floats). fl_krum_select: pairwise squared distances of rows 0..K-1, scores over
+// the min(max(1, K-f-2), K-1) nearest rows, the max(1, min(m, K)) best rows chosen; device outputs
+// dist[K*K] and score[K] (double) and coef[K] = w_i / sum of the chosen w (0 for the others).
+// fl_coef_mean: out rows 0..P-1 <- sum_k coef[k] * row k, coef in device memory (outputs may alias rows).
+unsigned fl_krum_grid(int64_t n, int K);
+void fl_krum_select(float* work, const RowPtrs& rows, const RowW& w, int K, int f, int m, int64_t n, double* dist, double* score, float* coef,
+                    hipStream_t s);
+void fl_coef_mean(const OutPtrs& outs, int P, const RowPtrs& rows, int K, const float* coef, int64_t n, hipStream_t s);
 // SCAFFOLD server step, packed buffer [Σ w_k dy_k | Σ w_k | Σ dc_k | K] (2n + 2 floats):
 //   reduce: buf <- the local contributions (before the cross-rank all-reduce)
 //   apply : out rows <- x_start + glr · buf[0:n] / buf[n];  c <- (c_init ? 0 : c) + buf[n+1:2n+1] / buf[2n+1]

@@ -297,6 +297,257 @@ __global__ __launch_bounds__(FL_BLOCK) void k_coordinate_median(OutPtrs outs, in
   }
 }
 
+// per-coordinate trimmed mean of K ≤ 16 models: the median's compare-exchange network, then the
+// kept values v[t .. K-t) summed in ascending order in fp32 and divided by K-2t (0 ≤ 2t < K, a
+// run-time argument). Loads every row's coordinate before any store: destinations may alias sources.
+template <int K>
+__global__ __launch_bounds__(FL_BLOCK) void k_trimmed_mean(OutPtrs outs, int P, RowPtrs rows, int t, int64_t n) {
+  const int64_t stride = (int64_t)gridDim.x * FL_BLOCK;
+  const float cnt = (float)(K - 2 * t);
+  for (int64_t i = blockIdx.x * FL_BLOCK + threadIdx.x; i < n; i += stride) {
+    float v[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = rows.p[k][i];
+#pragma unroll
+    for (int a = 0; a < K; ++a) {
+#pragma unroll
+      for (int b = 0; b < K - 1 - a; ++b) {
+        const float lo = fminf(v[b], v[b + 1]);
+        v[b + 1] = fmaxf(v[b], v[b + 1]);
+        v[b] = lo;
+      }
+    }
+    float s = 0.f;
+    // static register indices (a dynamic v[t + k] would put v in scratch)
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+      if (k >= t && k < K - t) s += v[k];
+    const float mean = s / cnt;
+    for (int p = 0; p < P; ++p) outs.p[p][i] = mean;
+  }
+}
+
+// (Multi-)Krum (Blanchard et al., 2017) in three launches, no cross-block synchronisation inside a
+// launch and no float atomics:
+//   k_pairwise_sqdist<K>: per block the K(K-1)/2 partial sums Σ (x_i − x_j)² of its coordinates,
+//                         stored into the block's slab of work[grid][K(K-1)/2]
+//   k_krum_select       : one block sums the slabs in a fixed order (double), scores every row,
+//                         selects, and writes dist / score / coef to device memory
+//   k_coef_mean<K>      : out rows <- Σ_k coef[k] · row_k, coef read from device memory
+// The distances come from differences: peers start a round from the same model, so rows differ
+// by ~1e-3 of their norm and |x_i|² + |x_j|² − 2 x_i·x_j has no correct digit in fp32.
+
+// Four consecutive coordinates 4g .. 4g+3 of a row. Rows are only guaranteed 4-byte aligned (row i
+// of a packed [k, n] buffer with odd n): the float4 access is taken only when the launcher found
+// every pointer 16-byte aligned. Both forms feed identical arithmetic, so a result does not depend
+// on where its rows happen to lie. Coordinates past n read as 0.
+template <bool VEC>
+__device__ __forceinline__ float4 load4(const float* p, int64_t g, int64_t n) {
+  const int64_t i = 4 * g;
+  if (VEC && i + 4 <= n) return reinterpret_cast<const float4*>(p)[g];
+  float4 v;
+  v.x = i < n ? p[i] : 0.f;
+  v.y = i + 1 < n ? p[i + 1] : 0.f;
+  v.z = i + 2 < n ? p[i + 2] : 0.f;
+  v.w = i + 3 < n ? p[i + 3] : 0.f;
+  return v;
+}
+
+template <bool VEC>
+__device__ __forceinline__ void store4(float* p, int64_t g, int64_t n, const float4& v) {
+  const int64_t i = 4 * g;
+  if (VEC && i + 4 <= n) {
+    reinterpret_cast<float4*>(p)[g] = v;
+    return;
+  }
+  if (i < n) p[i] = v.x;
+  if (i + 1 < n) p[i + 1] = v.y;
+  if (i + 2 < n) p[i + 2] = v.z;
+  if (i + 3 < n) p[i + 3] = v.w;
+}
+
+#define KRUM_WAVES (FL_BLOCK / 64)
+
+// Grid of k_pairwise_sqdist: a function of n and K only, so every rank reduces the identical
+// gathered buffer in the identical order and selects the same peers, bit for bit.
+// At most KRUM_MAX_GRID blocks (two per CU): K = 16 runs two waves per SIMD anyway, eight float4
+// loads in flight per thread keep HBM busy at that occupancy, and k_krum_select sums every slab.
+#define KRUM_MAX_GRID 512
+unsigned fl_krum_grid(int64_t n, int K) {
+  (void)K;
+  const unsigned g = grid_for((n + 3) / 4);
+  return g > KRUM_MAX_GRID ? KRUM_MAX_GRID : g;
+}
+
+template <int K, bool VEC>
+__global__ __launch_bounds__(FL_BLOCK) void k_pairwise_sqdist(float* __restrict__ work, RowPtrs rows, int64_t n) {
+  constexpr int NP = K * (K - 1) / 2;
+  __shared__ float part[KRUM_WAVES][NP];
+  float acc[NP];
+#pragma unroll
+  for (int q = 0; q < NP; ++q) acc[q] = 0.f;
+  const int64_t groups = (n + 3) / 4;
+  const int64_t stride = (int64_t)gridDim.x * FL_BLOCK;
+  for (int64_t g = (int64_t)blockIdx.x * FL_BLOCK + threadIdx.x; g < groups; g += stride) {
+    float4 v[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = load4<VEC>(rows.p[k], g, n);
+    int q = 0;
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+#pragma unroll
+      for (int j = i + 1; j < K; ++j) {
+        const float dx = v[i].x - v[j].x, dy = v[i].y - v[j].y, dz = v[i].z - v[j].z, dw = v[i].w - v[j].w;
+        acc[q] += (dx * dx + dy * dy) + (dz * dz + dw * dw);
+        ++q;
+      }
+    }
+  }
+  // wave reduction (xor butterfly: a fixed order), then the block's waves through LDS in wave order
+#pragma unroll
+  for (int q = 0; q < NP; ++q) {
+    float s = acc[q];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+    acc[q] = s;
+  }
+  const int wave = threadIdx.x / 64;
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int q = 0; q < NP; ++q) part[wave][q] = acc[q];
+  }
+  __syncthreads();
+  if (threadIdx.x < NP) {
+    float s = part[0][threadIdx.x];
+#pragma unroll
+    for (int w = 1; w < KRUM_WAVES; ++w) s += part[w][threadIdx.x];
+    work[(int64_t)blockIdx.x * NP + threadIdx.x] = s;  // every block stores its whole slab (zeros included)
+  }
+}
+
+// One block. Pair q of the slabs is (i, j), i < j, in the order k_pairwise_sqdist enumerates them.
+// The slabs are summed in double in a fixed two-level order: the block's threads split them into
+// C = KRUM_SELECT_BLOCK / NP chunks of consecutive slabs, each summed in slab order (eight loads in
+// flight), then the chunks in chunk order: the order depends on G and K only.
+// neighbours = min(max(1, K−f−2), K−1) smallest off-diagonal distances per row; the
+// max(1, min(m, K)) lowest scores are chosen, the lower index winning a tie; a NaN (a peer that
+// sent one) orders last, as numpy's sort does. coef[i] = w_i / Σ_chosen w, 0 for the others.
+#define KRUM_SELECT_BLOCK 1024
+__global__ __launch_bounds__(KRUM_SELECT_BLOCK) void k_krum_select(const float* __restrict__ work, int G, int K, int f, int m, RowW w,
+                                                                   double* __restrict__ dist, double* __restrict__ score, float* __restrict__ coef) {
+  __shared__ double d[16][16];
+  __shared__ double sc[16];
+  __shared__ int chosen[16];
+  __shared__ double part[KRUM_SELECT_BLOCK];
+  const int t = threadIdx.x;
+  const int NP = K * (K - 1) / 2;
+  if (t < 256) (&d[0][0])[t] = 0.0;
+  const int C = NP > 0 ? KRUM_SELECT_BLOCK / NP : 0;  // NP <= 120: at least 8 chunks
+  if (t < C * NP) {
+    const int p = t % NP, c = t / NP;
+    const int per = (G + C - 1) / C;
+    const int g1 = min(G, (c + 1) * per);
+    int g = c * per;
+    double s = 0.0;
+    for (; g + 8 <= g1; g += 8) {
+      float v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) v[u] = work[(int64_t)(g + u) * NP + p];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) s += (double)v[u];
+    }
+    for (; g < g1; ++g) s += (double)work[(int64_t)g * NP + p];
+    part[c * NP + p] = s;
+  }
+  __syncthreads();
+  if (t < NP) {
+    double s = 0.0;
+    for (int c = 0; c < C; ++c) s += part[c * NP + t];
+    int i = 0, rem = t;
+    while (rem >= K - 1 - i) {
+      rem -= K - 1 - i;
+      ++i;
+    }
+    const int j = i + 1 + rem;
+    d[i][j] = s;
+    d[j][i] = s;
+  }
+  __syncthreads();
+  for (int q = t; q < K * K; q += KRUM_SELECT_BLOCK) dist[q] = d[q / K][q % K];
+  if (t < K) {
+    int cnt = K - f - 2;
+    if (cnt < 1) cnt = 1;
+    if (cnt > K - 1) cnt = K - 1;
+    unsigned taken = 1u << t;
+    double s = 0.0;
+    for (int c = 0; c < cnt; ++c) {
+      int best = -1;
+      double bk = 0.0;
+      for (int j = 0; j < K; ++j) {
+        if ((taken >> j) & 1u) continue;
+        const double key = d[t][j] != d[t][j] ? __builtin_huge_val() : d[t][j];
+        if (best < 0 || key < bk) {
+          best = j;
+          bk = key;
+        }
+      }
+      taken |= 1u << best;
+      s += d[t][best];
+    }
+    sc[t] = s;
+    score[t] = s;
+  }
+  __syncthreads();
+  if (t < K) {
+    int want = m < K ? m : K;
+    if (want < 1) want = 1;
+    const double mine = sc[t] != sc[t] ? __builtin_huge_val() : sc[t];
+    int rank = 0;
+    for (int j = 0; j < K; ++j) {
+      const double other = sc[j] != sc[j] ? __builtin_huge_val() : sc[j];
+      if (other < mine || (other == mine && j < t)) ++rank;
+    }
+    chosen[t] = rank < want ? 1 : 0;
+  }
+  __syncthreads();
+  if (t < K) {
+    double ws = 0.0;
+    int cnt = 0;
+    float wt = 0.f;
+    for (int j = 0; j < K; ++j) {
+      const float wj = w.w[j];
+      if (j == t) wt = wj;
+      if (chosen[j]) {
+        ws += (double)wj;
+        ++cnt;
+      }
+    }
+    // all chosen weights 0 (no sample counts known): plain mean of the chosen rows
+    coef[t] = !chosen[t] ? 0.f : (ws > 0.0 ? (float)((double)wt / ws) : 1.f / (float)cnt);
+  }
+}
+
+// out rows 0..P-1 <- Σ_k coef[k] · row_k, k ascending, fma in fp32; rows of coefficient 0 are never
+// read. Every thread loads its coordinates from all rows before it stores: outputs may alias rows.
+template <int K, bool VEC>
+__global__ __launch_bounds__(FL_BLOCK) void k_coef_mean(OutPtrs outs, int P, RowPtrs rows, const float* __restrict__ coef, int64_t n) {
+  float c[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) c[k] = coef[k];
+  const int64_t groups = (n + 3) / 4;
+  const int64_t stride = (int64_t)gridDim.x * FL_BLOCK;
+  for (int64_t g = (int64_t)blockIdx.x * FL_BLOCK + threadIdx.x; g < groups; g += stride) {
+    float4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      if (c[k] == 0.f) continue;
+      const float4 v = load4<VEC>(rows.p[k], g, n);
+      acc.x = fmaf(c[k], v.x, acc.x); acc.y = fmaf(c[k], v.y, acc.y); acc.z = fmaf(c[k], v.z, acc.z); acc.w = fmaf(c[k], v.w, acc.w);
+    }
+    for (int p = 0; p < P; ++p) store4<VEC>(outs.p[p], g, n, acc);
+  }
+}
+
 // SCAFFOLD (Karimireddy et al.) server step in two launches around one all-reduce; float4 body,
 // scalar tail. Sums run in the same k order as the host reference.
 __global__ __launch_bounds__(FL_BLOCK) void k_scaffold_reduce(float* __restrict__ buf, RowPtrs dy, RowPtrs dc, RowW w, int K, int64_t n) {
@@ -393,6 +644,56 @@ void fl_coordinate_median(const OutPtrs& outs, int P, const RowPtrs& rows, int K
     default: break;
   }
 }
+void fl_trimmed_mean(const OutPtrs& outs, int P, const RowPtrs& rows, int K, int trim, int64_t n, hipStream_t s) {
+  const dim3 g(grid_for(n)), b(FL_BLOCK);
+  switch (K) {
+#define TRIM_CASE(KK) \
+  case KK: hipLaunchKernelGGL(k_trimmed_mean<KK>, g, b, 0, s, outs, P, rows, trim, n); break;
+    TRIM_CASE(1) TRIM_CASE(2) TRIM_CASE(3) TRIM_CASE(4) TRIM_CASE(5) TRIM_CASE(6) TRIM_CASE(7) TRIM_CASE(8)
+    TRIM_CASE(9) TRIM_CASE(10) TRIM_CASE(11) TRIM_CASE(12) TRIM_CASE(13) TRIM_CASE(14) TRIM_CASE(15) TRIM_CASE(16)
+#undef TRIM_CASE
+    default: break;
+  }
+}
+static bool all_aligned16(const RowPtrs& rows, int K, const OutPtrs* outs, int P) {
+  uintptr_t bits = 0;
+  for (int k = 0; k < K; ++k) bits |= reinterpret_cast<uintptr_t>(rows.p[k]);
+  for (int p = 0; outs != nullptr && p < P; ++p) bits |= reinterpret_cast<uintptr_t>(outs->p[p]);
+  return (bits & 15u) == 0;
+}
+void fl_krum_select(float* work, const RowPtrs& rows, const RowW& w, int K, int f, int m, int64_t n, double* dist, double* score, float* coef,
+                    hipStream_t s) {
+  const unsigned grid = K > 1 ? fl_krum_grid(n, K) : 0;
+  const bool vec = all_aligned16(rows, K, nullptr, 0);
+  const dim3 g(grid), b(FL_BLOCK);
+  switch (K) {
+#define DIST_CASE(KK)                                                                           \
+  case KK:                                                                                      \
+    if (vec) hipLaunchKernelGGL((k_pairwise_sqdist<KK, true>), g, b, 0, s, work, rows, n);      \
+    else hipLaunchKernelGGL((k_pairwise_sqdist<KK, false>), g, b, 0, s, work, rows, n);         \
+    break;
+    DIST_CASE(2) DIST_CASE(3) DIST_CASE(4) DIST_CASE(5) DIST_CASE(6) DIST_CASE(7) DIST_CASE(8)
+    DIST_CASE(9) DIST_CASE(10) DIST_CASE(11) DIST_CASE(12) DIST_CASE(13) DIST_CASE(14) DIST_CASE(15) DIST_CASE(16)
+#undef DIST_CASE
+    default: break;  // K == 1: no pair, nothing to measure
+  }
+  hipLaunchKernelGGL(k_krum_select, dim3(1), dim3(KRUM_SELECT_BLOCK), 0, s, work, (int)grid, K, f, m, w, dist, score, coef);
+}
+void fl_coef_mean(const OutPtrs& outs, int P, const RowPtrs& rows, int K, const float* coef, int64_t n, hipStream_t s) {
+  const bool vec = all_aligned16(rows, K, &outs, P);
+  const dim3 g(grid_for((n + 3) / 4)), b(FL_BLOCK);
+  switch (K) {
+#define COEF_CASE(KK)                                                                           \
+  case KK:                                                                                      \
+    if (vec) hipLaunchKernelGGL((k_coef_mean<KK, true>), g, b, 0, s, outs, P, rows, coef, n);   \
+    else hipLaunchKernelGGL((k_coef_mean<KK, false>), g, b, 0, s, outs, P, rows, coef, n);      \
+    break;
+    COEF_CASE(1) COEF_CASE(2) COEF_CASE(3) COEF_CASE(4) COEF_CASE(5) COEF_CASE(6) COEF_CASE(7) COEF_CASE(8)
+    COEF_CASE(9) COEF_CASE(10) COEF_CASE(11) COEF_CASE(12) COEF_CASE(13) COEF_CASE(14) COEF_CASE(15) COEF_CASE(16)
+#undef COEF_CASE
+    default: break;
+  }
+}
 void fl_scaffold_reduce(float* buf, const RowPtrs& dy, const RowPtrs& dc, const RowW& w, int K, int64_t n, hipStream_t s) {
   hipLaunchKernelGGL(k_scaffold_reduce, dim3(grid_for(n)), dim3(FL_BLOCK), 0, s, buf, dy, dc, w, K, n);
 }
@@ -414,5 +715,14 @@ void fl_scale_add_noise(float* t, int64_t n, float scale, float sigma, uint64_t 
 // kernels in flight (the first FedAvg launch blocked the host until the running epoch ended)
 extern "C" int myfyp_warm_fl_ops() {
   hipFuncAttributes attr;
-  return hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&k_weighted_sum)) == hipSuccess ? 0 : 1;
+  // the robust aggregators' launches of the headline peer count (8) resolve here too, so a first
+  // Krum / trimmed-mean round pays no lookup behind a running epoch
+  const void* fns[] = {reinterpret_cast<const void*>(&k_weighted_sum),
+                       reinterpret_cast<const void*>(&k_trimmed_mean<8>),
+                       reinterpret_cast<const void*>(&k_pairwise_sqdist<8, true>),
+                       reinterpret_cast<const void*>(&k_krum_select),
+                       reinterpret_cast<const void*>(&k_coef_mean<8, true>)};
+  for (const void* fn : fns)
+    if (hipFuncGetAttributes(&attr, fn) != hipSuccess) return 1;
+  return 0;
 }

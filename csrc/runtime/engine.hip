@@ -1010,6 +1010,48 @@ int myfyp_coordinate_median_multi(const uint64_t* outs, int P, const uint64_t* s
 int myfyp_coordinate_median(float* out, const uint64_t* srcs, int K, int64_t n, void* stream) {
   return myfyp_coordinate_median_multi((const uint64_t*)&out, 1, srcs, K, n, stream);
 }
+int myfyp_trimmed_mean_multi(const uint64_t* outs, int P, const uint64_t* srcs, int K, int trim, int64_t n, void* stream) {
+  if (!rows_ok(K, "trimmed_mean") || !rows_ok(P, "trimmed_mean outputs")) return 2;
+  if (trim < 0 || 2 * trim >= K) {
+    g_last_error = "trimmed_mean: 0 <= 2*trim < K";
+    return 2;
+  }
+  RowPtrs rows{};
+  OutPtrs o{};
+  for (int k = 0; k < K; ++k) rows.p[k] = reinterpret_cast<const float*>(srcs[k]);
+  for (int p = 0; p < P; ++p) o.p[p] = reinterpret_cast<float*>(outs[p]);
+  fl_trimmed_mean(o, P, rows, K, trim, n, (hipStream_t)stream);
+  CHECK_HIP(hipGetLastError());
+  return 0;
+}
+// Blocks of the Krum distance launch for n coordinates of K rows: the workspace of myfyp_krum_multi
+// holds myfyp_krum_grid(n, K) * K(K-1)/2 floats.
+int myfyp_krum_grid(int64_t n, int K) { return K > 1 ? (int)fl_krum_grid(n, K) : 0; }
+// Distances + selection (device outputs dist[K*K], score[K]: double; coef[K]: float), then, with
+// P > 0, out rows <- sum_k coef[k] * row k. w: HOST array of the K sample weights. Enqueues only.
+int myfyp_krum_multi(const uint64_t* outs, int P, const uint64_t* srcs, const float* w, int K, int f, int m, int64_t n, float* work, double* dist,
+                     double* score, float* coef, void* stream) {
+  if (!rows_ok(K, "krum") || (P != 0 && !rows_ok(P, "krum outputs"))) return 2;
+  if (n < 1 || dist == nullptr || score == nullptr || coef == nullptr || (K > 1 && work == nullptr)) {
+    g_last_error = "krum: n >= 1 and the work / dist / score / coef buffers are required";
+    return 2;
+  }
+  RowPtrs rows{};
+  OutPtrs o{};
+  RowW ww{};
+  for (int k = 0; k < K; ++k) {
+    rows.p[k] = reinterpret_cast<const float*>(srcs[k]);
+    ww.w[k] = w[k];
+  }
+  for (int p = 0; p < P; ++p) o.p[p] = reinterpret_cast<float*>(outs[p]);
+  fl_krum_select(work, rows, ww, K, f, m, n, dist, score, coef, (hipStream_t)stream);
+  CHECK_HIP(hipGetLastError());
+  if (P > 0) {
+    fl_coef_mean(o, P, rows, K, coef, n, (hipStream_t)stream);
+    CHECK_HIP(hipGetLastError());
+  }
+  return 0;
+}
 int myfyp_scaffold_reduce(float* buf, const uint64_t* dy, const uint64_t* dc, const float* w, int K, int64_t n, void* stream) {
   if (K < 0 || K > 16) {
     g_last_error = "scaffold_reduce supports 0..16 rows";

@@ -58,16 +58,21 @@ def trimmed_mean(param_lists: Sequence[Sequence], beta: float) -> List:
         raise ValueError("beta too large for the number of models")
     first = param_lists[0][0]
     out = []
-    for layer_idx in range(len(param_lists[0])):
-        if _is_torch(first):
-            import torch
+    if _is_torch(first):
+        import torch
 
-            stacked = torch.stack([p[layer_idx] for p in param_lists]).float()
-            s, _ = torch.sort(stacked, dim=0)
-            out.append(s[k : n - k].mean(dim=0).to(first.dtype))
-        else:
-            stacked = np.sort(np.stack([np.asarray(p[layer_idx]) for p in param_lists]), axis=0)
-            out.append(stacked[k : n - k].mean(axis=0).astype(stacked.dtype))
+        from myfyp_amd import ops
+
+        for layer_idx in range(len(param_lists[0])):
+            ref = param_lists[0][layer_idx]
+            srcs = [p[layer_idx].contiguous().float().reshape(-1) for p in param_lists]
+            dst = torch.empty_like(srcs[0])
+            ops.trimmed_mean_into(srcs, [dst], k)
+            out.append(dst.view_as(ref).to(ref.dtype))
+        return out
+    for layer_idx in range(len(param_lists[0])):
+        stacked = np.sort(np.stack([np.asarray(p[layer_idx]) for p in param_lists]), axis=0)
+        out.append(stacked[k : n - k].mean(axis=0).astype(stacked.dtype))
     return out
 
 

@@ -9,8 +9,10 @@ supported) or one remaining model.
 Fix: the reference releases an un-held lock on the empty-contributors path.
 
 Collective data plane: an aggregator also exposes ``collective_kind`` which tells the RCCL weights
-plane which reduction implements it (``"mean"`` → one weighted all-reduce, ``"median"`` →
-all-gather + per-coordinate median kernel, ``None`` → host fallback).
+plane which reduction implements it (``"mean"`` → one weighted all-reduce, ``"neighbor"`` →
+topology mixing, ``"scaffold"`` → packed all-reduce + apply, ``"median"`` / ``"trimmed_mean"`` →
+all-gather + per-coordinate sorting-network kernel, ``"krum"`` → all-gather + distance, selection
+and weighted-mean kernels, ``None`` → host fallback over gathered wire models).
 """
 
 from __future__ import annotations

@@ -16,13 +16,16 @@ class Krum(Aggregator):
     """Score each model by the summed squared distance to its ``n - f - 2`` nearest peers; average
     the ``m`` best (m=1 → classic Krum)."""
 
-    collective_kind = None
+    collective_kind = "krum"
 
     def __init__(self, node_name: str = "unknown", num_byzantine: int = 1, multi: int = 1) -> None:
         super().__init__(node_name)
         self.f = num_byzantine
         self.m = multi
         self.partial_aggregation = False
+        # set by the collective plane after a device aggregation: (trainer addresses in row order,
+        # coef device tensor); coef[i] == 0 means peer i was rejected. Reading coef synchronises.
+        self.last_selection = None
 
     def aggregate(self, models: List[P2PFLModel]) -> P2PFLModel:
         if not models:
@@ -30,17 +33,20 @@ class Krum(Aggregator):
         n = len(models)
         flats = [flatten(m.get_parameters()) for m in models]
         if _is_torch(flats[0]):
-            import torch
+            from myfyp_amd import ops
 
-            X = torch.stack(flats)
-            d = torch.cdist(X, X).pow(2).cpu().numpy()
+            # distances (from differences) and scores on the rows' device; only K scores reach the host
+            _, score, _ = ops.krum_into([f_.contiguous() for f_ in flats], [], [float(m.get_num_samples()) for m in models], self.f, self.m)
+            scores = score.cpu().numpy()
+            order = np.argsort(scores, kind="stable")
         else:
             X = np.stack(flats)
             sq = (X * X).sum(1)
             d = np.maximum(sq[:, None] + sq[None, :] - 2 * X @ X.T, 0)
-        k = max(1, n - self.f - 2)
-        scores = [np.sort(np.delete(d[i], i))[:k].sum() for i in range(n)]
-        chosen = [models[i] for i in np.argsort(scores)[: max(1, min(self.m, n))]]
+            k = max(1, n - self.f - 2)
+            scores = [np.sort(np.delete(d[i], i))[:k].sum() for i in range(n)]
+            order = np.argsort(scores)
+        chosen = [models[i] for i in order[: max(1, min(self.m, n))]]
         params = weighted_mean([m.get_parameters() for m in chosen], [m.get_num_samples() for m in chosen])
         contributors: List[str] = []
         for m in models:

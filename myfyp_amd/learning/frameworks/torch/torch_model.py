@@ -78,7 +78,8 @@ class TorchModel(P2PFLModel):
             return
         with torch.no_grad():
             for dst, src in zip(self._state_tensors(), params):
-                src_t = src if isinstance(src, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(src))
+                # (ascontiguousarray makes a 0-d array 1-d: BatchNorm's num_batches_tracked keeps its shape)
+                src_t = src if isinstance(src, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(src)).reshape(np.shape(src))
                 dst.copy_(src_t.to(dst.dtype), non_blocking=False)
 
     def build_copy(self, **kwargs) -> "TorchModel":

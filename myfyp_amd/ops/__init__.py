@@ -10,6 +10,9 @@ Ops
 * ``stacked_weighted_sum`` / ``broadcast_rows`` — reductions over a ``[P, N]`` stacked flat buffer
   (co-located peers) feeding / consuming the RCCL all-reduce
 * ``coordinate_median`` — FedMedian (register sorting network, K ≤ 16)
+* ``trimmed_mean_into`` — coordinate-wise trimmed mean (the median's sorting network, K ≤ 16)
+* ``krum_into`` — (Multi-)Krum: pairwise squared distances from differences, selection and the
+  weighted mean of the chosen rows, all on the device (K ≤ 16); returns ``(dist, score, coef)``
 * ``adam_step`` / ``sgd_step`` — fused optimizers over a flat buffer, optionally with the FedProx
   proximal term and the SCAFFOLD control-variate correction fused in (K5, K8, K13)
 * ``scale_add_noise`` — attack injection (sign flip / Gaussian noise, K14)
@@ -29,6 +32,8 @@ __all__ = [
     "stacked_weighted_sum",
     "broadcast_rows",
     "coordinate_median",
+    "trimmed_mean_into",
+    "krum_into",
     "adam_step",
     "sgd_step",
     "scale_add_noise",
@@ -155,6 +160,95 @@ def median_into(rows: Sequence[torch.Tensor], outs: Sequence[torch.Tensor]) -> N
     med = s[(k - 1) // 2] if k % 2 else 0.5 * (s[k // 2 - 1] + s[k // 2])
     for o in outs:
         o.copy_(med)
+
+
+def _native_rows(rows: Sequence[torch.Tensor], outs: Sequence[torch.Tensor]) -> bool:
+    """Rows and outputs the row-pointer kernels take: device, <= 16 each, contiguous fp32."""
+    return (rows[0].device.type == "cuda" and len(rows) <= 16 and len(outs) <= 16
+            and all(t.is_contiguous() and t.dtype == torch.float32 for t in [*rows, *outs]))
+
+
+def trimmed_mean_into(rows: Sequence[torch.Tensor], outs: Sequence[torch.Tensor], trim: int) -> None:
+    """``outs[p] = mean(sorted(rows)[trim : K - trim])`` per coordinate for 1-D fp32 rows
+    (``0 <= 2·trim < K``); on the GPU one launch (``k_trimmed_mean<K>``) for K <= 16 rows and
+    <= 16 outputs, which may alias the rows. Elsewhere: sort and mean in float64 (the oracle)."""
+    k = len(rows)
+    trim = int(trim)
+    if trim < 0 or 2 * trim >= k:
+        raise ValueError(f"trimmed mean of {k} rows cannot drop {trim} from each end")
+    if _native_rows(rows, outs):
+        if not outs:
+            return
+        src, keep_s = _host_ptrs(rows)
+        dst, keep_d = _host_ptrs(outs)
+        _native.check(_lib().myfyp_trimmed_mean_multi(dst, len(outs), src, k, trim, rows[0].numel(), _stream()), "trimmed_mean_multi")
+        return
+    s, _ = torch.sort(torch.stack([r.double() for r in rows]), dim=0)
+    mean = s[trim : k - trim].sum(dim=0) / (k - 2 * trim)
+    for o in outs:
+        o.copy_(mean)
+
+
+def krum_neighbours(k: int, f: int) -> int:
+    """Distances a Krum score sums: the ``K - f - 2`` nearest rows, at least 1, at most the K - 1 others."""
+    return min(max(1, k - int(f) - 2), k - 1)
+
+
+def krum_into(rows: Sequence[torch.Tensor], outs: Sequence[torch.Tensor], weights: Sequence[float], f: int, m: int):
+    """(Multi-)Krum over 1-D fp32 rows: squared distances from differences, per row the score over
+    its :func:`krum_neighbours` nearest rows, the ``max(1, min(m, K))`` lowest scores chosen (the
+    lower index wins a tie, a NaN score orders last), ``outs[p] = Σ_k coef[k]·rows[k]`` with
+    ``coef[k] = w_k / Σ_chosen w`` (0 for the others). Returns ``(dist [K, K] float64, score [K]
+    float64, coef [K] float32)`` on the rows' device; ``outs=[]`` gives the selection only.
+
+    On the GPU (K <= 16 rows, <= 16 outputs, which may alias the rows) it is three launches —
+    ``k_pairwise_sqdist<K>``, ``k_krum_select``, ``k_coef_mean<K>`` — that only enqueue: the host
+    learns the selection when it reads a returned tensor. Elsewhere: float64 torch math (the oracle)."""
+    k = len(rows)
+    if len(weights) != k:
+        raise ValueError(f"{k} rows but {len(weights)} weights")
+    dev = rows[0].device
+    if _native_rows(rows, outs):
+        lib = _lib()
+        n = rows[0].numel()
+        pairs = k * (k - 1) // 2
+        work = torch.empty(max(1, int(lib.myfyp_krum_grid(n, k)) * pairs), dtype=torch.float32, device=dev)
+        dist = torch.empty(k, k, dtype=torch.float64, device=dev)
+        score = torch.empty(k, dtype=torch.float64, device=dev)
+        coef = torch.empty(k, dtype=torch.float32, device=dev)
+        src, keep_s = _host_ptrs(rows)
+        dst, keep_d = _host_ptrs(outs)
+        w = (ctypes.c_float * k)(*[float(x) for x in weights])
+        _native.check(lib.myfyp_krum_multi(dst, len(outs), src, ctypes.cast(w, ctypes.c_void_p), k, int(f), int(m), n, work.data_ptr(), dist.data_ptr(),
+                                           score.data_ptr(), coef.data_ptr(), _stream()), "krum_multi")
+        return dist, score, coef
+    x = [r.double() for r in rows]
+    dist = torch.zeros(k, k, dtype=torch.float64, device=dev)
+    for i in range(k):
+        for j in range(i + 1, k):
+            dist[i, j] = dist[j, i] = (x[i] - x[j]).square().sum()
+    cnt = krum_neighbours(k, f)
+    score = torch.zeros(k, dtype=torch.float64, device=dev)
+    inf = float("inf")
+    for i in range(k):
+        others = [float(dist[i, j]) for j in range(k) if j != i]
+        others.sort(key=lambda v: inf if v != v else v)  # stable; NaN last
+        score[i] = float(sum(others[:cnt]))  # ascending order
+    sc = [float(v) for v in score]
+    order = sorted(range(k), key=lambda i: (inf if sc[i] != sc[i] else sc[i], i))
+    chosen = sorted(order[: max(1, min(int(m), k))])
+    wsum = float(sum(float(weights[i]) for i in chosen))
+    coef64 = torch.zeros(k, dtype=torch.float64)
+    for i in chosen:
+        coef64[i] = float(weights[i]) / wsum if wsum > 0 else 1.0 / len(chosen)
+    coef = coef64.float().to(dev)
+    if outs:
+        mean = torch.zeros_like(x[0])
+        for i in chosen:
+            mean += float(coef[i]) * x[i]
+        for o in outs:
+            o.copy_(mean)
+    return dist, score, coef
 
 
 def scaffold_reduce(buf: torch.Tensor, dys: Sequence[torch.Tensor], dcs: Sequence[torch.Tensor], weights: Sequence[float]) -> None:

@@ -40,6 +40,9 @@ _SIGNATURES = {
     "myfyp_broadcast_rows": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p]),
     "myfyp_coordinate_median": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p]),
     "myfyp_coordinate_median_multi": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_void_p]),
+    "myfyp_trimmed_mean_multi": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int64, c_void_p]),
+    "myfyp_krum_grid": (c_int, [c_int64, c_int]),
+    "myfyp_krum_multi": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "myfyp_scaffold_reduce": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
     "myfyp_scaffold_apply": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_float, c_int64, c_void_p]),
     # optimizers over flat buffers

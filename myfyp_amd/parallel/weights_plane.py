@@ -730,7 +730,7 @@ def _mesh_neighbors(fed: Federation, peers, index, w, local, learners) -> None:
 
 
 # aggregator kinds reduced on the device (no wire models, no host copies)
-DEVICE_KINDS = ("mean", "neighbor", "scaffold", "median")
+DEVICE_KINDS = ("mean", "neighbor", "scaffold", "median", "krum", "trimmed_mean")
 
 
 def _scaffold_cb(learner):
@@ -935,6 +935,169 @@ def _median(fed: Federation, arrived: Dict[str, Tuple[float, Any]]) -> None:
         ops.median_into(rows, [med])
         for a in addrs:
             _unpack_into(learners[a], med)
+
+
+# ---------------------------------------------------------------------------------------------
+# robust aggregation: coordinate-wise trimmed mean and (Multi-)Krum
+# ---------------------------------------------------------------------------------------------
+ROBUST_MAX_ROWS = 16  # rows the device kernels take (ops.trimmed_mean_into / ops.krum_into)
+
+
+@traced("aggregate_trimmed_mean")
+def aggregate_trimmed_mean(fed: Federation, arrived: Dict[str, Tuple[float, Any]], aggregator) -> None:
+    """Coordinate-wise trimmed mean of the trainers' models on the device (host math:
+    ``_math.trimmed_mean``), laid out as :func:`aggregate_median`: the local trainers' rows packed
+    into a [k_max, n] buffer, ONE all-gather over the live ranks, ONE ``k_trimmed_mean<K>`` launch
+    into every local peer. ``trim = floor(beta·K)`` with K this round's trainers; ``2·trim >= K``
+    raises the host aggregator's ``ValueError`` on every rank, before any collective."""
+    t0 = time.perf_counter()
+    fed.run_aggregation(lambda: _robust(fed, arrived, aggregator, "trimmed_mean"))
+    fed.record("aggregate", time.perf_counter() - t0)
+
+
+@traced("aggregate_krum")
+def aggregate_krum(fed: Federation, arrived: Dict[str, Tuple[float, Any]], aggregator) -> None:
+    """(Multi-)Krum over the trainers' models on the device (host math: ``Krum.aggregate``): the
+    all-gather of :func:`aggregate_median`, then ``ops.krum_into`` — distances from differences,
+    selection and the sample-weighted mean of the chosen rows written into every local peer, the
+    selection never leaving the device on the round's path. Every rank reduces the same gathered
+    buffer with the same grid, so all of them choose the same peers, bit for bit. Afterwards every
+    local node's aggregator carries ``last_selection = (trainer addresses in row order, coef)``;
+    ``coef`` is the device tensor (reading it is the caller's synchronisation), 0 for a rejected peer."""
+    t0 = time.perf_counter()
+    fed.run_aggregation(lambda: _robust(fed, arrived, aggregator, "krum"))
+    fed.record("aggregate", time.perf_counter() - t0)
+
+
+def _trim_count(aggregator, k: int) -> int:
+    trim = int(np.floor(aggregator.beta * k))
+    if 2 * trim >= k:
+        raise ValueError("beta too large for the number of models")
+    return trim
+
+
+def _robust_into(kind: str, aggregator, rows, outs, ws):
+    """The device op of ``kind``; Krum returns its ``coef`` device tensor."""
+    with torch.no_grad():
+        if kind == "trimmed_mean":
+            ops.trimmed_mean_into(rows, outs, _trim_count(aggregator, len(rows)))
+            return None
+        return ops.krum_into(rows, outs, ws, aggregator.f, aggregator.m)[2]
+
+
+def _int_buffers(learner) -> List[torch.Tensor]:
+    return [b for b in learner.model.get_model().buffers() if not b.is_floating_point()]
+
+
+def _row_fns(learners, kind: str):
+    """(live, row_of): ``live`` when a peer's model is its flat parameter vector alone, so the
+    kernels read and write the live rows; otherwise ``row_of`` packs a copy (flat parameters, then
+    the floating buffers ``_unpack_into`` takes back). The host ``Krum`` measures every tensor of
+    ``get_parameters()`` — the whole ``state_dict``, BatchNorm's integer ``num_batches_tracked``
+    included — so the Krum row carries those counters too, behind everything that is unpacked: the
+    device and the host then score the same vector and select the same peers."""
+    live = all(len(state_tensors(lr)) == 1 and not (kind == "krum" and _int_buffers(lr)) for lr in learners)
+    if live:
+        return True, lambda lr: lr.flat_params()
+    if kind == "krum":
+        return False, lambda lr: torch.cat([_pack(lr)] + [b.detach().reshape(-1).float() for b in _int_buffers(lr)])
+    return False, _pack
+
+
+def _publish_selection(fed: Federation, addrs, aggregator, order, coef) -> None:
+    if coef is None:
+        return
+    aggregator.last_selection = (list(order), coef)
+    for a in addrs:
+        if a in fed.local_nodes:
+            fed.local_nodes[a].aggregator.last_selection = (list(order), coef)
+
+
+def _robust(fed: Federation, arrived: Dict[str, Tuple[float, Any]], aggregator, kind: str) -> None:
+    if fed.mesh is not None:  # (a one-device mesh too: its collectives still run through RCCL)
+        mut = _MeshMutation(fed, list(arrived))
+        _mesh_robust(fed, arrived, aggregator, kind)
+        if mut.before:
+            mut.apply()
+        return
+    addrs = [a for a in arrived if a in fed.local_nodes]
+    learners = {a: fed.local_nodes[a].learner for a in addrs}
+    trainers = [a for a in addrs if float(arrived[a][0]) > 0]
+    # every rank learns K, the row order (rank, then local order) and the sample weights
+    gathered = fed.all_gather_object([(a, float(arrived[a][0])) for a in trainers])
+    counts = [len(g) for g in gathered]
+    order = [a for g in gathered for a, _ in g]
+    ws = [w for g in gathered for _, w in g]
+    if not order:
+        return
+    if kind == "trimmed_mean":
+        _trim_count(aggregator, len(order))  # the same K on every rank: all of them raise, or none
+    live, row_of = _row_fns(list(learners.values()), kind)
+
+    def reduce_rows(rows) -> None:
+        if live:
+            coef = _robust_into(kind, aggregator, rows, [learners[a].flat_params() for a in addrs], ws)
+        else:
+            res = torch.empty_like(rows[0])
+            coef = _robust_into(kind, aggregator, rows, [res], ws)
+            for a in addrs:
+                _unpack_into(learners[a], res)
+        _publish_selection(fed, addrs, aggregator, order, coef)
+
+    if fed.solo:  # every trainer is local: straight from the live rows into every peer
+        reduce_rows([row_of(learners[a]) for a in trainers])
+        return
+    kmax = max(1, max(counts))
+    ref = row_of(learners[addrs[0]])
+    n = ref.numel()
+    send = torch.zeros(kmax, n, dtype=torch.float32, device=ref.device)
+    for i, a in enumerate(trainers):
+        send[i].copy_(row_of(learners[a]))
+    recv = torch.empty(len(counts) * kmax, n, dtype=torch.float32, device=ref.device)
+    fed.all_gather_into_tensor_(recv, send)
+    reduce_rows([recv[r * kmax + i] for r, c in enumerate(counts) for i in range(c)])
+
+
+def _mesh_robust(fed: Federation, arrived: Dict[str, Tuple[float, Any]], aggregator, kind: str) -> None:
+    """Trimmed mean / Krum over a device mesh, in the manner of ``_mesh_median``: every device
+    packs its trainers' rows ([k_max, n], zero-padded), ONE mesh all-gather, then per device the op
+    into a result vector unpacked into its peers. Every device reduces the same gathered rows in the
+    same order, so a Krum selection is the same on all of them."""
+    addrs = [a for a in arrived if a in fed.local_nodes]
+    learners = [fed.local_nodes[a].learner for a in addrs]
+    ranks = _by_mesh_rank(fed, addrs, learners)
+    trainers = {r: [(a, lr) for a, lr in v if float(arrived[a][0]) > 0] for r, v in ranks.items()}
+    counts = [len(trainers[r]) for r in fed.mesh_members]
+    order = [a for r in fed.mesh_members for a, _ in trainers[r]]
+    ws = [float(arrived[a][0]) for a in order]
+    if not order:
+        return
+    if kind == "trimmed_mean":
+        _trim_count(aggregator, len(order))
+    _, row_of = _row_fns(learners, kind)
+    kmax = max(counts)
+    n = row_of(learners[0]).numel()
+    sends, recvs = [], []
+    for r in fed.mesh_members:
+        dev = fed.devices[r]
+        with on_device(dev):
+            s_ = torch.zeros(kmax, n, dtype=torch.float32, device=dev)
+            for i, (a, lr) in enumerate(trainers[r]):
+                s_[i].copy_(row_of(lr))
+            sends.append(s_)
+            recvs.append(torch.empty(len(counts) * kmax, n, dtype=torch.float32, device=dev))
+    fed.mesh.all_gather_(recvs, sends)
+    fed.mesh_track(f"{kind} all_gather")
+    for r, recv in zip(fed.mesh_members, recvs):
+        if not ranks[r]:
+            continue
+        with on_device(fed.devices[r]):
+            rows = [recv[q * kmax + i] for q, c in enumerate(counts) for i in range(c)]
+            res = torch.empty(n, dtype=torch.float32, device=recv.device)
+            coef = _robust_into(kind, aggregator, rows, [res], ws)
+            for _, lr in ranks[r]:
+                _unpack_into(lr, res)
+            _publish_selection(fed, [a for a, _ in ranks[r]], aggregator, order, coef)
 
 
 def aggregate_generic(fed: Federation, arrived: Dict[str, Tuple[float, Any]], aggregator) -> Any:

@@ -25,8 +25,8 @@ def join_aggregation(state, learner, aggregator, trainer: bool) -> None:
     final = state.total_rounds is None or round_ + 1 >= state.total_rounds
 
     def leader(arrived):
-        device_path = kind in ("scaffold", "median") and _agree_device_path(f, kind, arrived)
-        if kind in ("scaffold", "median") and not device_path:
+        device_path = kind in _VOTED_KINDS and _agree_device_path(f, kind, arrived)
+        if kind in _VOTED_KINDS and not device_path:
             arrived = _with_wire_models(f, arrived)
         if kind == "mean":
             total, contributors = weights_plane.aggregate_mean(f, arrived, final=final)
@@ -39,6 +39,12 @@ def join_aggregation(state, learner, aggregator, trainer: bool) -> None:
             extra = None
         elif kind == "median" and device_path:
             weights_plane.aggregate_median(f, arrived)
+            extra = None
+        elif kind == "trimmed_mean" and device_path:
+            weights_plane.aggregate_trimmed_mean(f, arrived, aggregator)
+            extra = None
+        elif kind == "krum" and device_path:
+            weights_plane.aggregate_krum(f, arrived, aggregator)
             extra = None
         else:
             weights_plane.aggregate_generic(f, arrived, aggregator)
@@ -54,13 +60,23 @@ def join_aggregation(state, learner, aggregator, trainer: bool) -> None:
     model.set_contribution(list(state.train_set) or [state.addr], max(1, model.num_samples))
 
 
+# kinds whose device path the ranks vote on each round (the others always have one)
+_VOTED_KINDS = ("scaffold", "median", "trimmed_mean", "krum")
+
+
 def _agree_device_path(f, kind: str, arrived) -> bool:
-    """SCAFFOLD / FedMedian reduce on the device only when EVERY rank's peers are device learners
-    (flat parameter buffers): the ranks agree on it through one control-plane gather, so all of
-    them issue the same collectives (a rank whose local peers happen to be non-trainers cannot
-    tell from its own, empty, payloads)."""
-    local_ok = all(hasattr(f.local_nodes[a].learner, "flat_params") for a in arrived if a in f.local_nodes)
-    return all(f.all_gather_object(bool(local_ok)))
+    """SCAFFOLD / FedMedian / TrimmedMean / Krum reduce on the device only when EVERY rank's peers
+    are device learners (flat parameter buffers): the ranks agree on it through one control-plane
+    gather, so all of them issue the same collectives (a rank whose local peers happen to be
+    non-trainers cannot tell from its own, empty, payloads). The trimmed-mean and Krum kernels take
+    at most ``ROBUST_MAX_ROWS`` rows: the gather also carries every rank's trainer count, and more
+    trainers than that in the round send every rank to the generic path."""
+    local = [a for a in arrived if a in f.local_nodes]
+    local_ok = all(hasattr(f.local_nodes[a].learner, "flat_params") for a in local)
+    if kind not in ("trimmed_mean", "krum"):
+        return all(f.all_gather_object(bool(local_ok)))
+    votes = f.all_gather_object((bool(local_ok), sum(1 for a in local if arrived[a][0] > 0)))
+    return all(ok for ok, _ in votes) and sum(c for _, c in votes) <= weights_plane.ROBUST_MAX_ROWS
 
 
 def _with_wire_models(f, arrived):
