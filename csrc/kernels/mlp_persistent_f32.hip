@@ -28,11 +28,31 @@
 // f32 MFMA chain over the batch as the head's, and the same optimizer code: it stays bit-identical
 // to the head's rows with no W2 traffic at all (checked by a GPU test through `w2chk`).
 //
-// Per step three hand-offs (persist_common.h): H1 slices owners → heads (16 × 4 KB; write-through
-// stores + drained flag + sc1 loads), partial logits head ↔ head (8 × 4 KB) and dH2 slices heads →
-// owners (8 × 4 KB, double-buffered by step parity because the owners re-read the previous step's
-// tile for their deferred W2-replica update) — the last two as LL (value, tag) pairs: no producer
-// drain, workgroup meet or flag store, the consumer's data load is its readiness check.
+// Per step three hand-offs (persist_common.h): H1 slices owners → heads (16 × 4 KB), partial logits
+// head ↔ head (8 × 4 KB) and dH2 slices heads → owners (8 × 4 KB, double-buffered by step parity
+// because the owners re-read the previous step's tile for their deferred W2-replica update). All
+// three are flag hand-offs: payload stores, every storing wave drains them, the workgroup meets, one
+// lane stores the flag; the consumer's wave 0 polls the flags, the workgroup meets and reads the
+// payload with L1-bypassing (sc1) loads. A gang found on one XCD at kernel entry
+// (persist::gang_same_xcd; every K-split-1 gang under round-robin dispatch) keeps payloads and flags
+// in that XCD's L2 with plain stores, any other writes them through (MYFYP_F32_PLAIN_PUB). The LL
+// (value, tag) pair protocol is still in the file for each hand-off (P32_LL_H1 / P32_LL_PL /
+// P32_LL_DH2) and is off (the dH2 measurement is noted at LLD in owner32).
+//
+// One owner step t (K split 1, fused forward — the default where instantiated, MYFYP_F32_FWD_FUSE):
+//   H1(0) comes from a prologue before the step loop (fwd_all + h1_publish), then per step
+//   1. the deferred W2-replica update of step t − 1, and a touch of the next batch's columns (L2);
+//   2. wait for dH2(t) of the 8 heads, load it to LDS;
+//   3. C1: dH1 partials per wave, cross-wave sum, relu mask, exact three-term bf16 split to LDS;
+//   4. C2, per wave over its own K steps q: dW1 MFMAs, optimizer update of the K step's weights,
+//      the K step's columns of X(t + 1) staged into the X tile — and, with a step to follow, the
+//      forward MFMAs of that K step for H1(t + 1) on what the wave has just written (its registers
+//      and its own LDS stores: no barrier);
+//   5. H1(t + 1): partials → LDS, ONE barrier (it also ends the step), cross-wave sum in wave order,
+//      relu, rows past the batch zeroed, stores to the exchange slab of parity (t + 1) & 1, flag.
+//   With the separate forward (switch 0, K splits > 1, extra-term epochs, layout 3) step t instead
+//   starts with the whole forward of H1(t) (K loop, reduction, publish) after the barrier that ends
+//   C2 of step t − 1. Both orders add the same terms in the same order: H1 is bit-identical.
 #include <atomic>
 
 #include "mlp_persistent.h"
@@ -160,8 +180,22 @@ constexpr int SMR = (P32_SM8 && !P32_LL_PL) ? 2 : 4;  // softmax rows per lane
 #define P32_LL_DH2 0
 #endif
 constexpr int H1W = P32_LL_H1 ? 2 : 1;  // floats per H1 exchange element (value, tag)
-// (measured and not kept: the next step's forward accumulated inside C2 — 16.8 us/step vs 15.7,
-// C2 4.6 -> 6.6 us and 14 more VGPR spills)
+// The next step's forward accumulated inside C2 (owner32's FUSE; docs/PERFORMANCE.md "Fused next-step
+// forward", profiles/r7_fwd_fuse). An early attempt lost on registers: 16.8 us/step vs 15.7,
+// C2 4.6 -> 6.6 us, 14 more VGPR spills. Now: the bench instantiation <64, Adam> holds the 16
+// accumulators at 256 VGPRs, 0 spills, 0 scratch (the separate forward: 245). What spilled at first
+// (16 VGPRs) was not C2's working set but loop-invariant values hoisted out of the step loop — the
+// publish block's LDS / exchange addresses, the next-batch row address and the f64 conversions of
+// the Adam betas — removed by laundering the lane index per use (and the betas per step). Measured,
+// 8 peers: the forward's K loop is 1.44 us of the separate forward's 2.40 (reduce + stores 0.68,
+// flag 0.28). Fused in place, C2 grew by exactly that (3.80 -> 5.24 us): every K step is a chain
+// load X(t+1) -> store -> forward reads -> MFMAs, and the K steps sit in separate basic blocks, so
+// nothing overlapped; the step still lost the barrier and the hand-off after C2 (13.16 -> 12.86 us,
+// 655-657 vs 641-642 rounds/s). With the X(t+1) loads issued one K step ahead (K step 0's before the
+// dH2 wait; xq_load) C2 + forward is 4.88 us, the step 12.74 us, 674-679 rounds/s; with the forward
+// K step's four A-fragment reads batched and its MFMAs interleaved over the tiles as well (fwd_kstep)
+// the step is 12.48 us: 683.2 / 681.5 / 683.9 vs 639.9 / 639.3 / 638.5 rounds/s with the separate
+// forward (the parent's build: 639.5).
 constexpr int NCG = 16;  // W1 column groups per peer (D1 / 16)
 constexpr int NH = 8;    // heads per peer (D2 / 16)
 constexpr int KSMAX = 8;
@@ -343,8 +377,11 @@ __device__ __forceinline__ bool gang_commit(const MLPArgs& a, const MLPPersistF3
   return persist::wg_wait(pb.flags, FPP, p, FD, NR, pb.fbase + DONE_MARK, pb.err, sOk);
 }
 
-template <int BP, bool ADAM, bool EXTRA, int KS, bool RH>
+template <int BP, bool ADAM, bool EXTRA, int KS, bool RH, bool FUSE = false>
 __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, int g, char* smem, unsigned gen) {
+  // FUSE: the forward of step t + 1 is accumulated inside C2 of step t, K step by K step, by the wave
+  // that has just updated that K step's weights and staged its columns of the next batch
+  static_assert(!FUSE || (KS == 1 && !RH && !EXTRA && !P32_LL_H1 && !P32_BALANCE && !P32_XSWZ), "fused forward: layout 1, K split 1, no extra term");
   constexpr int MT = BP / 16;
   constexpr int RQ = rq_of(KS);
   constexpr int XPT = BP / 4;  // 16-byte X chunks per lane: 4 K steps x BP rows x 4 chunks / 64 lanes
@@ -515,6 +552,24 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
     for (int j = 0; j < 8; ++j) wq[j] = q < RQ ? w1[q < RQ ? q : 0][j] : sW1x[cq * 32 + kappa(hq, j)];
     bf16x8 bh, bm, bl;
     split3(wq, bh, bm, bl);
+    if constexpr (FUSE) {
+      // fused loop: the A fragments of all batch tiles read first, then the tiles' MFMAs interleaved
+      // term by term (each accumulator still adds lo, mid, hi in that order): one LDS round trip and
+      // independent MFMAs back to back instead of MT times read -> wait -> three dependent MFMAs
+      bf16x8 af[MT];
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) {
+        const bf16* xp = sX + (16 * mt + cq) * LDX + 32 * s + 4 * (hq & 1);
+        af[mt] = cat8(*reinterpret_cast<const bf16x4*>(xp + ((hq >> 1) << 3)), *reinterpret_cast<const bf16x4*>(xp + ((2 + (hq >> 1)) << 3)));
+      }
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) acc[mt] = mfma_bf16(af[mt], bl, acc[mt]);
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) acc[mt] = mfma_bf16(af[mt], bm, acc[mt]);
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) acc[mt] = mfma_bf16(af[mt], bh, acc[mt]);
+      return;
+    }
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
       if (lds_step && mt != wave) continue;  // wave-uniform
@@ -525,45 +580,32 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
       acc[mt] = mfma3(af, bh, bm, bl, acc[mt]);
     }
   };
-  if (tid == 0) sOk[1] = 1;  // LL bulk-load verdict (0: a wave gave up)
-  __syncthreads();  // sW1x written
-
-  persist::BiasCorr bc;
-  bc.init(o, ctl.z);
-  float lr_t = 0.f, inv_bc2 = 0.f;
-  for (int t = 0; t < nsteps; ++t) {
-    int tv = tid;  // per-iteration opaque thread index (addresses re-derived each step: VGPR pressure)
-    asm volatile("" : "+v"(tv));
-    const int rows = rows_at(a, n, t);
-    const float lr_prev = lr_t, inv_prev = inv_bc2;  // step t - 1 (the deferred W2-replica update)
-    const unsigned tag = persist::ll_tag(gen, pb.fbase, t);
-#if P32_RUNNING_BC
-    bc.next(o, lr_t, inv_bc2);
-#else
-    persist::bias_corr(o, ctl.z, t, lr_t, inv_bc2);
-#endif
-    float* sH1c = sH1 + (t & 1) * BP * 16;
-    if (g == 0) P32_STAMP(0, t, 0);
-
-    // ================= A: H1 slice = relu(X · W1sliceᵀ + b1), split-K over the 8 waves
-    {
-      f32x4 acc[MT];
+  // the wave's whole forward contribution (the separate forward; the fused loop's prologue)
+  auto fwd_all = [&](f32x4(&acc)[MT]) {
 #pragma unroll
-      for (int mt = 0; mt < MT; ++mt) acc[mt] = zero4();
+    for (int mt = 0; mt < MT; ++mt) acc[mt] = zero4();
 #pragma unroll
-      for (int q = 0; q < (KS == 1 ? RQ + 1 : RQ); ++q) {
-        fwd_kstep(q, acc);
-        if (P32_SB_FWD) __builtin_amdgcn_sched_barrier(0);
-      }
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) sRed[(wave * MT + mt) * 64 + lane] = acc[mt];
+    for (int q = 0; q < (KS == 1 ? RQ + 1 : RQ); ++q) {
+      fwd_kstep(q, acc);
+      if (P32_SB_FWD) __builtin_amdgcn_sched_barrier(0);
     }
-    lds_barrier();
-    if (tid < MT * 64) {
-      const int mt = tid >> 6, hh = (tid & 63) >> 4, cc = tid & 15;
-      f32x4 s = sRed[mt * 64 + (tid & 63)];
+  };
+  // H1(t) from the waves' partial sums: cross-wave reduction in wave order 0..7, relu, rows past the
+  // batch zeroed, into sH1 parity t & 1 and the exchange slab of that parity, then the flag
+  // (value fbase + t + 1). XR: then the K parts' reduction inside the XCD. false: the gang gave up.
+  auto h1_publish = [&](int t, const f32x4(&acc)[MT]) -> bool {
+    const int rows = rows_at(a, n, t);
+    float* sH1c = sH1 + (t & 1) * BP * 16;
+    int tq = tid;  // laundered: the LDS and exchange addresses hoisted out of the step loop would be spilled
+    asm volatile("" : "+v"(tq));
 #pragma unroll
-      for (int w = 1; w < 8; ++w) s += sRed[(w * MT + mt) * 64 + (tid & 63)];
+    for (int mt = 0; mt < MT; ++mt) sRed[(wave * MT + mt) * 64 + (tq & 63)] = acc[mt];
+    lds_barrier();
+    if (tq < MT * 64) {
+      const int mt = tq >> 6, hh = (tq & 63) >> 4, cc = tq & 15;
+      f32x4 s = sRed[mt * 64 + (tq & 63)];
+#pragma unroll
+      for (int w = 1; w < 8; ++w) s += sRed[(w * MT + mt) * 64 + (tq & 63)];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int b = 16 * mt + 4 * hh + i;
@@ -571,9 +613,9 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
         const float v = b < rows ? (KS == 1 ? fmaxf(s[i], 0.f) : s[i]) : 0.f;
         sH1c[b * 16 + cc] = v;
 #if P32_LL_H1
-        persist::ll_st1p(pb.plain, h1x_part(pb, p, kh, t, BP) + 2 * ((int64_t)b * PD1 + NCG * cg + cc), v, tag);
+        persist::ll_st1p(pb.plain, h1x_part(pb, p, kh, t, BP) + 2 * ((int64_t)b * PD1 + NCG * cg + cc), v, persist::ll_tag(gen, pb.fbase, t));
 #else
-        persist::pub32(pb.plain, h1x_part(pb, p, kh, t, BP) + (int64_t)b * PD1 + NCG * cg + cc, v);
+        persist::pub32(pb.plain, h1x_part(pb, p, kh, t, BP) + (unsigned)(b * PD1 + NCG * cg + cc), v);
 #endif
       }
     }
@@ -585,7 +627,7 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
       // the column group's KS partials, all on this XCD (plain when the placement check passed):
       // summed in kh order and relu'd by every owner of the group (same bits in each); K part 0
       // hands the reduced slice to the heads, written through (they sit on the peer's first XCD)
-      if (!persist::wg_wait(pb.flags, FPP, p, F_H1P + cg * KS, KS, pb.fbase + (unsigned)(t + 1), pb.err, sOk)) return;
+      if (!persist::wg_wait(pb.flags, FPP, p, F_H1P + cg * KS, KS, pb.fbase + (unsigned)(t + 1), pb.err, sOk)) return false;
       if (tid < BP * 4) {
         const int b = tid >> 2, c4 = 4 * (tid & 3);
         float4 u[KS];
@@ -611,6 +653,41 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
         __syncthreads();  // the reduced slice is in sH1c for every wave
     }
     if (g == 0) P32_STAMP(0, t, 2);
+    return true;
+  };
+  if (tid == 0) sOk[1] = 1;  // LL bulk-load verdict (0: a wave gave up)
+  __syncthreads();  // sW1x written
+
+  if (FUSE && nsteps > 0) {  // H1(0); every later H1(t + 1) comes out of step t's C2
+    f32x4 acc[MT];
+    fwd_all(acc);
+    if (!h1_publish(0, acc)) return;
+  }
+
+  persist::BiasCorr bc;
+  bc.init(o, ctl.z);
+  float lr_t = 0.f, inv_bc2 = 0.f;
+  for (int t = 0; t < nsteps; ++t) {
+    int tv = tid;  // per-iteration opaque thread index (addresses re-derived each step: VGPR pressure)
+    asm volatile("" : "+v"(tv));
+    const float lr_prev = lr_t, inv_prev = inv_bc2;  // step t - 1 (the deferred W2-replica update)
+    const unsigned tag = persist::ll_tag(gen, pb.fbase, t);
+#if P32_RUNNING_BC
+    bc.next(o, lr_t, inv_bc2);
+#else
+    persist::bias_corr(o, ctl.z, t, lr_t, inv_bc2);
+#endif
+    float* sH1c = sH1 + (t & 1) * BP * 16;
+    if (g == 0) P32_STAMP(0, t, 0);
+
+    // ================= A: H1 slice = relu(X · W1sliceᵀ + b1), split-K over the 8 waves (fused loop:
+    //                    H1(t) was published from the prologue or from step t - 1's C2)
+    if constexpr (!FUSE) {
+      f32x4 acc[MT];
+      fwd_all(acc);
+      if (g == 0) P32_STAMP(0, t, 7);  // K-step loop | reduction, stores and flag
+      if (!h1_publish(t, acc)) return;
+    }
 
     // the previous step's W2-replica update runs while the heads work on this step's H1 (layout 3:
     // W2 is updated in step t's C phase and published for the heads)
@@ -625,6 +702,7 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
       // direct X: this lane's next-batch row (lane < BP) through the epoch index; wave 0 leaves the
       // indices in LDS for C2's staging (read after the dH2 barriers below)
       int xi = lane;
+      if (FUSE) asm volatile("" : "+v"(xi));  // (a hoisted 64-bit row address was spilled)
       if (xd) {
         xi = (lane < rows_n && lane < BP) ? xidx_p[(t + 1) * a.B + lane] : 0;
         int ln = lane;  // laundered: a hoisted LDS address was the bench instantiation's one VGPR spill
@@ -642,6 +720,32 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
       }
       asm volatile("" ::"v"(sink));
     }
+
+    // fused loop: the next batch's columns come through a buffer resource that ends with the batch's
+    // last row (0 bytes on the last step), so rows past it and, with the offset forced out of range,
+    // columns past D0 load as zero without a branch. K step q + 1's loads are issued right after K
+    // step q's chunks are stored, ahead of its forward, and K step 0's here, ahead of the dH2 wait:
+    // their L2 latency runs under the wait and under the previous K step instead of in front of
+    // every K step's store.
+    constexpr bool FUSEX = FUSE && !xd;
+    constexpr int XQF = FUSEX ? BP / 16 : 1;
+    uint4 xqf[XQF];
+    const __amdgpu_buffer_rsrc_t r_xn =
+        rsrc_of(a.Xb16 + ((int64_t)p * a.xb_rows + (int64_t)(t + 1) * a.B) * D0, more ? rows_at(a, n, t + 1) * D0 * 2 : 0);
+    auto xq_load = [&](int q) {
+      const int s = wave + 8 * q;
+      if (s >= KS1) return;  // wave-uniform
+      int lx = lane;
+      asm volatile("" : "+v"(lx));
+#pragma unroll
+      for (int kk = 0; kk < XQF; ++kk) {
+        const int idx = kk * 64 + lx;
+        const int r = idx >> 2, gcol = C0 + 32 * s + 8 * (idx & 3);
+        const unsigned off = gcol < D0 ? (unsigned)(r * D0 + gcol) * 2u : 0x7FFFFFF0u;
+        xqf[kk] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r_xn, off, 0, 0));
+      }
+    };
+    if constexpr (FUSEX) xq_load(0);
 
     // ================= C: backward of this slice
     const float* dh2_t = pb.dh2x + ((int64_t)p * 2 + (t & 1)) * BP * PD2 * 2;
@@ -774,6 +878,9 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
     {
       int lv = lane;
       asm volatile("" : "+v"(lv));
+      f32x4 accF[FUSE ? MT : 1];  // fused loop: this wave's share of H1(t + 1)
+#pragma unroll
+      for (int mt = 0; mt < (FUSE ? MT : 1); ++mt) accF[mt] = zero4();
       const int rows_next = more ? rows_at(a, n, t + 1) : 0;
       const bf16* xnext = xd ? xp16 : a.Xb16 + ((int64_t)p * a.xb_rows + (int64_t)(t + 1) * a.B) * D0;
 #pragma unroll
@@ -799,6 +906,10 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
           uint4 xq[XQ];
 #pragma unroll
           for (int kk = 0; kk < XQ; ++kk) {
+            if constexpr (FUSEX) {  // loaded ahead (xq_load)
+              xq[kk] = xqf[FUSEX ? kk : 0];
+              continue;
+            }
             const int idx = kk * 64 + lv;
             const int r = idx >> 2, col = 32 * s + 8 * (idx & 3), gcol = C0 + col;
 #ifdef P32_EXP_NOX  // timing experiment: no next-batch staging loads
@@ -857,10 +968,31 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
             }
           }
         }
+        // fused loop: the K step's weights are updated and its columns of X(t + 1) staged, both by
+        // this wave (its own registers and LDS writes, which complete in order): no barrier
+        if constexpr (FUSE) {
+          if constexpr (FUSEX) {
+            if (q + 1 < (KS == 1 ? RQ + 1 : RQ)) xq_load(q + 1);
+          }
+          if (more) fwd_kstep(q, accF);
+        }
+      }
+      if constexpr (FUSE) {
+        if (g == 0) P32_STAMP(0, t, 6);
+        // H1(t + 1): sRed is free (C1's partials were consumed before C1's last barrier), and so is
+        // the exchange slab of parity (t + 1) & 1 (the heads read H1(t - 1) before they produced
+        // dH2(t)). The reduction's barrier is the one that ends the step.
+        if (more) {
+          if (!h1_publish(t + 1, accF)) return;
+        } else {
+          __syncthreads();
+        }
       }
     }
-    __syncthreads();
-    if (g == 0) P32_STAMP(0, t, 6);
+    if constexpr (!FUSE) {
+      __syncthreads();
+      if (g == 0) P32_STAMP(0, t, 6);
+    }
   }
 
   if (!gang_commit<KS, RH, BP>(a, pb, p, g, sOk)) return;
@@ -1759,7 +1891,7 @@ __device__ void headr32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
 // flags offset by RETRY_BASE (the aborted attempt's flag values are all smaller), and on success
 // sets err[p] = 2 ("recovered"). Gangs are independent: one peer's give-up never aborts another.
 
-template <int BP, bool ADAM, bool EXTRA, int KS, bool RH = false>
+template <int BP, bool ADAM, bool EXTRA, int KS, bool RH = false, bool FUSE = false>
 __global__ __launch_bounds__(NT) void mlp_persistent_f32_epoch(MLPArgs a, MLPPersistF32Bufs pb, int p_base, int attempt) {
   extern __shared__ __attribute__((aligned(16))) char smem_p32[];
   constexpr int PPL = ppl_of(KS, RH);
@@ -1824,7 +1956,7 @@ __global__ __launch_bounds__(NT) void mlp_persistent_f32_epoch(MLPArgs a, MLPPer
     if (role == 0 && threadIdx.x == 0 && p < 64) g_plain_seen[p] = pb.plain;
   }
   if (role < ng_of(KS))
-    owner32<BP, ADAM, EXTRA, KS, RH>(a, pb, p, role, smem_p32, gen);
+    owner32<BP, ADAM, EXTRA, KS, RH, FUSE>(a, pb, p, role, smem_p32, gen);
   else if (RH)
     headr32<BP, ADAM, EXTRA, KS>(a, pb, p, role - ng_of(KS), smem_p32, gen);
   else
@@ -2049,10 +2181,12 @@ bool v3_supported(const MLPArgs& a) {
   return persistent_f32_lds_ks(a, 1, true) <= 160 * 1024;
 }
 
-template <int BP, bool ADAM, bool EXTRA, int KS, bool RH = false>
+template <int BP, bool ADAM, bool EXTRA, int KS, bool RH = false, bool FUSE = false>
 const void* f32_fn() {
-  return (const void*)mlp_persistent_f32_epoch<BP, ADAM, EXTRA, KS, RH>;
+  return (const void*)mlp_persistent_f32_epoch<BP, ADAM, EXTRA, KS, RH, FUSE>;
 }
+// the fused forward (owner32's FUSE) is instantiated for layout 1 at K split 1 without an extra term
+__host__ __device__ constexpr bool fuse_inst(int KS, bool RH) { return KS == 1 && !RH && !P32_LL_H1 && !P32_BALANCE; }
 template <int BP, int KS, bool RH = false>
 hipError_t prepare_f32_bp(int lds) {
   const void* fns[4] = {f32_fn<BP, true, false, KS, RH>(), f32_fn<BP, true, true, KS, RH>(), f32_fn<BP, false, false, KS, RH>(),
@@ -2061,13 +2195,26 @@ hipError_t prepare_f32_bp(int lds) {
     const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) return e;
   }
+  if constexpr (fuse_inst(KS, RH)) {
+    for (const void* fn : {f32_fn<BP, true, false, KS, RH, true>(), f32_fn<BP, false, false, KS, RH, true>()}) {
+      const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+      if (e != hipSuccess) return e;
+    }
+  }
   return hipSuccess;
 }
 template <int BP, int KS, bool RH = false>
-void launch_f32_bp(const MLPArgs& a, const MLPPersistF32Bufs& pb, hipStream_t s, int p_base, size_t lds, int attempt) {
+void launch_f32_bp(const MLPArgs& a, const MLPPersistF32Bufs& pb, hipStream_t s, int p_base, size_t lds, int attempt, bool fuse) {
   const dim3 grid(grid_of(KS, RH, RH ? roles3_of(KS, BP) : roles_of(KS))), block(NT);
   const bool adam = a.opt.kind == 0;
   const bool extra = a.anchor != nullptr || a.cg != nullptr;
+  if constexpr (fuse_inst(KS, RH)) {
+    if (fuse && !extra) {
+      if (adam) hipLaunchKernelGGL((mlp_persistent_f32_epoch<BP, true, false, KS, RH, true>), grid, block, lds, s, a, pb, p_base, attempt);
+      else hipLaunchKernelGGL((mlp_persistent_f32_epoch<BP, false, false, KS, RH, true>), grid, block, lds, s, a, pb, p_base, attempt);
+      return;
+    }
+  }
   if (adam && !extra) hipLaunchKernelGGL((mlp_persistent_f32_epoch<BP, true, false, KS, RH>), grid, block, lds, s, a, pb, p_base, attempt);
   else if (adam) hipLaunchKernelGGL((mlp_persistent_f32_epoch<BP, true, true, KS, RH>), grid, block, lds, s, a, pb, p_base, attempt);
   else if (!extra) hipLaunchKernelGGL((mlp_persistent_f32_epoch<BP, false, false, KS, RH>), grid, block, lds, s, a, pb, p_base, attempt);
@@ -2210,6 +2357,24 @@ extern "C" int mlp_debug_plain_seen(int* out) {
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_plain_seen), sizeof(g_plain_seen)) == hipSuccess ? 0 : 1;
 }
 
+// MYFYP_F32_FWD_FUSE: 1 (default) the owners accumulate the next step's forward inside C2 where that
+// loop is instantiated (layout 1, K split 1, no extra term), 0 the separate forward (A/B);
+// mlp_set_f32_fwd_fuse overrides it (tests; -1: back to the environment). mlp_f32_fwd_fuse_last: the
+// path the last layout-1/3 epoch launch took (1 fused, 0 separate, -1 none yet).
+static std::atomic<int> g_fuse_override{-1};
+static std::atomic<int> g_fuse_last{-1};
+static int f32_fwd_fuse_mode() {
+  const int o = g_fuse_override.load(std::memory_order_relaxed);
+  if (o >= 0) return o;
+  static const int v = [] {
+    const char* e = getenv("MYFYP_F32_FWD_FUSE");
+    return e != nullptr ? atoi(e) : 1;
+  }();
+  return v;
+}
+extern "C" int mlp_set_f32_fwd_fuse(int mode) { return g_fuse_override.exchange(mode < 0 ? -1 : mode); }
+extern "C" int mlp_f32_fwd_fuse_last() { return g_fuse_last.load(std::memory_order_relaxed); }
+
 hipError_t mlp_launch_persistent_f32_epoch(const MLPArgs& a, const MLPPersistF32Bufs& pb_in, hipStream_t s, bool zero_flags, const int* active) {
   MLPPersistF32Bufs pb = pb_in;
   pb.plain_ok = mlp_plain_pub_mode();
@@ -2226,6 +2391,8 @@ hipError_t mlp_launch_persistent_f32_epoch(const MLPArgs& a, const MLPPersistF32
   const bool rh = f32_variant(a) == 3;
   const int ppl = ppl_of(KS, rh);
   const size_t lds = persistent_f32_lds_ks(a, KS, rh);
+  const bool fuse = f32_fwd_fuse_mode() != 0 && fuse_inst(KS, rh) && a.anchor == nullptr && a.cg == nullptr;
+  g_fuse_last.store(fuse ? 1 : 0, std::memory_order_relaxed);
   // groups of ppl peers: one launch each (a launch's gangs must all be co-resident), then the
   // recovery launches (attempt 1): a no-op exit for every gang that did not give up
   // (a group with no active peer is not launched: at one peer per device and K split 8 the other
@@ -2242,22 +2409,22 @@ hipError_t mlp_launch_persistent_f32_epoch(const MLPArgs& a, const MLPPersistF32
       if (!group_live(p0)) continue;
       if (rh) {
         if (KS == 2) {
-          if (a.Bpad == 64) launch_f32_bp<64, 2, true>(a, pb, s, p0, lds, attempt);
-          else launch_f32_bp<32, 2, true>(a, pb, s, p0, lds, attempt);
+          if (a.Bpad == 64) launch_f32_bp<64, 2, true>(a, pb, s, p0, lds, attempt, fuse);
+          else launch_f32_bp<32, 2, true>(a, pb, s, p0, lds, attempt, fuse);
         } else {
-          if (a.Bpad == 64) launch_f32_bp<64, 1, true>(a, pb, s, p0, lds, attempt);
-          else launch_f32_bp<32, 1, true>(a, pb, s, p0, lds, attempt);
+          if (a.Bpad == 64) launch_f32_bp<64, 1, true>(a, pb, s, p0, lds, attempt, fuse);
+          else launch_f32_bp<32, 1, true>(a, pb, s, p0, lds, attempt, fuse);
         }
       } else if (KS == 8) {
-        launch_f32_bp<64, 8>(a, pb, s, p0, lds, attempt);  // (f32_ks_wanted: Bpad 64 only)
+        launch_f32_bp<64, 8>(a, pb, s, p0, lds, attempt, fuse);  // (f32_ks_wanted: Bpad 64 only)
       } else if (KS == 4) {
-        launch_f32_bp<64, 4>(a, pb, s, p0, lds, attempt);
+        launch_f32_bp<64, 4>(a, pb, s, p0, lds, attempt, fuse);
       } else if (KS == 2) {
-        if (a.Bpad == 64) launch_f32_bp<64, 2>(a, pb, s, p0, lds, attempt);
-        else launch_f32_bp<32, 2>(a, pb, s, p0, lds, attempt);
+        if (a.Bpad == 64) launch_f32_bp<64, 2>(a, pb, s, p0, lds, attempt, fuse);
+        else launch_f32_bp<32, 2>(a, pb, s, p0, lds, attempt, fuse);
       } else {
-        if (a.Bpad == 64) launch_f32_bp<64, 1>(a, pb, s, p0, lds, attempt);
-        else launch_f32_bp<32, 1>(a, pb, s, p0, lds, attempt);
+        if (a.Bpad == 64) launch_f32_bp<64, 1>(a, pb, s, p0, lds, attempt, fuse);
+        else launch_f32_bp<32, 1>(a, pb, s, p0, lds, attempt, fuse);
       }
     }
   return hipGetLastError();

@@ -364,8 +364,12 @@ struct BiasCorr {
   }
   // advance to the next optimizer step k and return lr / (1 - β1^k), 1 / sqrt(1 - β2^k)
   __device__ __forceinline__ void next(const OptParams& o, float& lr_t, float& inv) {
-    b1k = uniform_f64(b1k * (double)o.beta1);
-    b2k = uniform_f64(b2k * (double)o.beta2);
+    // (the betas laundered per step: their f64 conversions hoisted out of the step loop each took a
+    // VGPR pair for the whole epoch)
+    float b1 = o.beta1, b2 = o.beta2;
+    asm volatile("" : "+s"(b1), "+s"(b2));
+    b1k = uniform_f64(b1k * (double)b1);
+    b2k = uniform_f64(b2k * (double)b2);
     lr_t = uniform_f32((float)((double)o.lr / (1.0 - b1k)));
     inv = uniform_f32((float)(1.0 / sqrt(1.0 - b2k)));
   }

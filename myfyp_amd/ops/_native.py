@@ -109,6 +109,8 @@ _SIGNATURES = {
     "myfyp_warm_all": (c_int, [c_int]),
     "mlp_set_plain_pub": (c_int, [c_int]),  # single-XCD hand-off mode override (-1: MYFYP_F32_PLAIN_PUB)
     "mlp_debug_plain_seen": (c_int, [c_void_p]),
+    "mlp_set_f32_fwd_fuse": (c_int, [c_int]),  # owners' fused next-step forward: 1 / 0 (-1: MYFYP_F32_FWD_FUSE)
+    "mlp_f32_fwd_fuse_last": (c_int, []),  # path of the last fp32 layout-1/3 epoch launch (1 fused, 0 separate)
     "mlp_debug_stamps": (c_int, [c_void_p]),  # only in the -DMLP_STAMPS diagnostics build
     "mlp_debug_persistent_f32_stamps": (c_int, [c_void_p]),  # likewise
 }

@@ -40,19 +40,34 @@ torch.cuda.synchronize()
 st = np.zeros((2, 128, 10), dtype=np.uint64)  # g_p32_stamps[2][128][10]
 assert lib.mlp_debug_persistent_f32_stamps(st.ctypes.data) == 0
 st = st.astype(np.int64)
-print("owner: fwd+reduce | H1 publish | W2 replica | wait dH2 | dH2 load+C1+split | C2 (dW1+Adam+X) | step")
+fuse_last = getattr(lib, "mlp_f32_fwd_fuse_last", None)
+fused = fuse_last is not None and fuse_last() == 1
+print("owner forward:", "fused into C2 (MYFYP_F32_FWD_FUSE=1)" if fused else "separate")
+# owner stamps of step t. Separate forward: 0 step start, 7 forward K loop done, 1 reduced + stored,
+# 2 flag published, 3 W2 replica done, 4 dH2 seen, 5 C1 done, 6 C2 done (after the step's barrier).
+# Fused: 0 step start, 3, 4, 5 as above, 6 C2 with the fused forward done (this wave's, no barrier),
+# then H1(t + 1)'s reduction and publish, stamped as step t + 1's 1 and 2.
+if fused:
+    print("owner: W2 replica | wait dH2 | dH2 load+C1+split | C2 + fused fwd | reduce+stores | flag publish | step")
+else:
+    print("owner: fwd K loop | reduce+stores | flag publish | W2 replica | wait dH2 | dH2 load+C1+split | C2 (dW1+Adam+X) | step")
 print("head : wait H1 | H1 load | H2+PL | PL publish | wait PL | softmax | dH2+publish | off-path | step")
 rows = []
 for t in range(2, 14):
-    o, h = st[0, t], st[1, t]
-    do = np.diff(o[:7]) / 100.0
+    o, h, o1 = st[0, t], st[1, t], st[0, t + 1]
+    if fused:
+        seq = [o[0], o[3], o[4], o[5], o[6], o1[1], o1[2]]
+    else:
+        seq = [o[0], o[7], o[1], o[2], o[3], o[4], o[5], o[6]]
+    do = np.diff(np.array(seq)) / 100.0
     dh = np.diff(h[:9]) / 100.0
-    step_o = (st[0, t + 1, 0] - o[0]) / 100.0
+    step_o = (o1[0] - o[0]) / 100.0
     step_h = (st[1, t + 1, 0] - h[0]) / 100.0
     rows.append(np.concatenate([do, [step_o], dh, [step_h]]))
     print(f"t={t:2d} owner {' '.join(f'{x:5.2f}' for x in do)} | {step_o:5.2f}   head {' '.join(f'{x:5.2f}' for x in dh)} | {step_h:5.2f}")
 m = np.median(np.array(rows), axis=0)
-print("median owner", " ".join(f"{x:5.2f}" for x in m[:7]), " head", " ".join(f"{x:5.2f}" for x in m[7:]))
-print("owner H1 published -> head H1 seen (us):", [round((st[1, t, 1] - st[0, t, 2]) / 100.0, 2) for t in range(2, 10)])
+no = len(do) + 1
+print("median owner", " ".join(f"{x:5.2f}" for x in m[:no]), " head", " ".join(f"{x:5.2f}" for x in m[no:]))
+print("owner H1 published -> head H1 seen (us; fused: negative while the head is still in step t - 1):", [round((st[1, t, 1] - st[0, t, 2]) / 100.0, 2) for t in range(2, 10)])
 print("head dH2 published -> owner dH2 seen (us):", [round((st[0, t, 4] - st[1, t, 7]) / 100.0, 2) for t in range(2, 10)])
 print("head PL published -> head PL all seen (us):", [round((st[1, t, 5] - st[1, t, 4]) / 100.0, 2) for t in range(2, 10)])
