@@ -1427,6 +1427,13 @@ __device__ __forceinline__ void wgrad_store(const WgradArgs& a, const f32x4 (&ac
   }
 }
 
+// Contract of all three weight-gradient kernels for a split without rows (kbeg >= kend: a peer with
+// nb = 0, or the trailing splits of a partial batch): the workgroup returns before the store, so
+//   accumulate = 1: nothing is added — the slab keeps the zeros the optimizer left (zero_after);
+//   accumulate = 0: the slab is NOT zeroed — a peer with nb = 0 keeps the previous step's gradient.
+// Nothing may consume that stale slab: cnn_opt_step, the only reader, skips a peer whose nb is 0
+// (k_opt_step's `active`), and the next step that has rows stores over it. A new reader of the
+// Wf-layout gradient has to apply the same nb mask (tests/test_conv_gpu.py pins the behaviour).
 template <int BM, int BN, bool PRO>
 __global__ __launch_bounds__(256) void k_conv_wgrad(WgradArgs a, int tiles_m, int tiles_n, int splits) {
   constexpr int FM = BM / 32, FN = BN / 32;       // fragments per wave
@@ -1978,6 +1985,9 @@ extern "C" int conv_gemm_launch(int mode, const ConvGemmArgs* pa, int peers, voi
   if ((a.src_c & 7) || (a.ncol & 7) || peers < 1 || !(mode == 0 || mode == 1 || mode == 4 || mode == 5)) return 1;
   if ((mode == 4 || mode == 5) && a.pro_ss != nullptr) return 1;
   if ((mode == 4 && a.stride != 1) || (mode == 5 && (a.stride != 2 || !conv_dma_enabled()))) return 1;
+  // mode 4 takes ONE pad for both axes (R-1-pad and S-1-pad of the conv): a non-square filter's
+  // dgrad cannot be expressed that way and goes through mode 1
+  if (mode == 4 && a.R != a.S) return 1;
   // the buffer-load gathers form 32-bit byte offsets within one peer's source and weights
   if (CONV_BUFLOAD && ((int64_t)a.max_batch * a.src_h * a.src_w * a.src_c * 2 >= INT32_MAX ||
                        (int64_t)a.ncol * a.R * a.S * a.src_c * 2 >= INT32_MAX))

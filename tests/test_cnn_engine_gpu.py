@@ -79,6 +79,15 @@ def test_conv_fwd_dgrad_wgrad_vs_torch(cin, cout, k, stride, pad, h, n, conv_dma
     assert y.view(n, ho, ho, cpo)[..., cout:].abs().max().item() == 0 if cpo > cout else True
     st = stats.view(-1, 2, cpo).sum(0)
     torch.testing.assert_close(st[0, :cout], ref.sum((0, 1, 2)), atol=0.5, rtol=2e-2)
+    # the sum of squares is taken over the fp32 values before the bf16 rounding, like `ref`: two fp32
+    # evaluations of one sum of positive terms. Worst case per element: (K / 32 + 2) fp32 roundings of a
+    # partial sum <= sum |x w| ~ sqrt(K) |y|, so 2 * 74 * 2^-24 * 48 = 4e-4 relative on y^2 at K = 2304
+    sq_ref = ref.pow(2).sum((0, 1, 2))
+    sq_tol = dict(atol=1e-3 * float(sq_ref.max()), rtol=1e-3)
+    print(f"sum x^2: worst |err| / tolerance {float(((st[1, :cout] - sq_ref).abs() / (sq_tol['atol'] + 1e-3 * sq_ref.abs())).max()):.4f}")
+    torch.testing.assert_close(st[1, :cout], sq_ref, **sq_tol)  # MI355X: worst |err| / tolerance 0.0002
+    with pytest.raises(AssertionError):  # control: the sum over all but the last output row must fail
+        torch.testing.assert_close(st[1, :cout], ref[:, :-1].pow(2).sum((0, 1, 2)) if ho > 1 else sq_ref * 0.9, **sq_tol)
     _check_fused_bn_finalize_fwd(lib, a, stats, st, cout, cpo, n * ho * ho)
 
     # dgrad
@@ -775,6 +784,12 @@ def test_conv_grouped_peers_with_uneven_batches(mode, conv_dma, cout, h):
         if mode == 0:
             st = stats[p].view(rows, 2, ncol).sum(0)
             torch.testing.assert_close(st[0, :cout], refs[p][:n].sum((0, 2, 3)), atol=0.5, rtol=2e-2)
+            sq_ref = refs[p][:n].pow(2).sum((0, 2, 3))  # fp32 values before the rounding, as in `refs`
+            sq_tol = dict(atol=1e-3 * float(sq_ref.max()), rtol=1e-3)
+            print(f"sum x^2: worst |err| / tolerance {float(((st[1, :cout] - sq_ref).abs() / (sq_tol['atol'] + 1e-3 * sq_ref.abs())).max()):.4f}")
+            torch.testing.assert_close(st[1, :cout], sq_ref, **sq_tol)  # MI355X: worst |err| / tolerance 0.0002
+            with pytest.raises(AssertionError):  # control: the sum over all but the last output row must fail
+                torch.testing.assert_close(st[1, :cout], refs[p][:n, :, :-1].pow(2).sum((0, 2, 3)), **sq_tol)
 
 
 @pytest.mark.parametrize("h,n", [(32, 2), (32, 3)])
