@@ -28,9 +28,9 @@ hipError_t mlp_launch_persistent_epoch(const MLPArgs& a, const MLPPersistBufs& p
 //      gangs of 16 owners + 8 heads, one launch per group of 8 peers.
 struct MLPPersistF32Bufs {
   float* h1x;       // [P][Bpad][256]      owner g -> heads: H1 columns 16g..16g+15
-  float* plx;       // [P][8][Bpad*16][2]  head hd -> heads: partial logits over its H2 slice, LL (value, tag) pairs
-  float* dh2x;      // [P][2][Bpad][128][2] head hd -> owners: dH2 columns 16hd..16hd+15 (step parity), LL pairs
-  unsigned* gen;    // [P] epoch generation of the LL tags (advanced by every completed epoch)
+  float* plx;       // [P][8][Bpad*16][2]  head hd -> heads: partial logits over its H2 slice (sized for (value, tag) pairs)
+  float* dh2x;      // [P][2][Bpad][128][2] head hd -> owners: dH2 columns 16hd..16hd+15 (step parity; sized for pairs)
+  unsigned* gen;    // [P] epoch generation (advanced by every completed epoch; it tagged the LL pairs, nothing reads it now)
   unsigned* flags;  // [P][32][32] one 128-B line per flag (16 H1, 8 PL, 8 dH2); zeroed per launch
   size_t flag_bytes;
   int* err;         // give-up words: [0,64) per peer first attempt (1 gave up, 2 recovered), [64,128) retry
@@ -47,14 +47,11 @@ bool mlp_persistent_f32_supported(const MLPArgs& a);
 size_t mlp_persistent_f32_h1x_floats(int P, int Bpad);  // H1-partial exchange region at the start of the buffer
 size_t mlp_persistent_f32_bytes(int P, int Bpad);
 size_t mlp_persistent_f32_flag_bytes(int P);
-int mlp_persistent_f32_gang();
+int mlp_persistent_f32_gang();  // workgroups (CUs) per peer
 int mlp_persistent_f32_resident_capacity(const MLPArgs& a, int num_cus);
 int mlp_persistent_f32_launch_wgs(const MLPArgs& a);  // workgroups of one epoch launch
-int mlp_persistent_f32_ks(const MLPArgs& a);
-int mlp_persistent_f32_variant(const MLPArgs& a);
-// 1: this build's fp32 epoch for `a` reads X directly (needs a.Xp16 and the index kernel's xidx / Yb)
-int mlp_persistent_f32_x_direct(const MLPArgs& a);
-int mlp_persistent_f32_x_direct_build();  // the build's P32_XDIRECT  // gang layout: 1 owners + heads, 2 owners only          // K split of the owners (1 or 2)             // workgroups (CUs) per peer
+int mlp_persistent_f32_ks(const MLPArgs& a);       // K split of the owners (1, 2, 4 or 8)
+int mlp_persistent_f32_variant(const MLPArgs& a);  // gang layout: 1 owners + heads, 2 owners only, 3 row heads
 int mlp_persistent_f32_flags_per_peer();   // u32 words per peer in the flag block
 // flag block layout: u32 per flag line, flag lines per peer, and how many of each peer's last lines
 // use every word (the gang placement slots); every other line's flag is its word 0

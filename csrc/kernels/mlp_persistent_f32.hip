@@ -35,9 +35,9 @@
 // lane stores the flag; the consumer's wave 0 polls the flags, the workgroup meets and reads the
 // payload with L1-bypassing (sc1) loads. A gang found on one XCD at kernel entry
 // (persist::gang_same_xcd; every K-split-1 gang under round-robin dispatch) keeps payloads and flags
-// in that XCD's L2 with plain stores, any other writes them through (MYFYP_F32_PLAIN_PUB). The LL
-// (value, tag) pair protocol is still in the file for each hand-off (P32_LL_H1 / P32_LL_PL /
-// P32_LL_DH2) and is off (the dH2 measurement is noted at LLD in owner32).
+// in that XCD's L2 with plain stores, any other writes them through (MYFYP_F32_PLAIN_PUB). An LL
+// (value, tag) pair protocol was tried for each hand-off and measured no faster (profiles/r3e_ll_ab,
+// profiles/r5_ll, profiles/r6_xr/ll_dh2); its code last existed in commit f8de7cf.
 //
 // One owner step t (K split 1, fused forward — the default where instantiated, MYFYP_F32_FWD_FUSE):
 //   H1(0) comes from a prologue before the step loop (fwd_all + h1_publish), then per step
@@ -111,75 +111,32 @@ using persist::row_min16;
 using persist::row_sum16;
 using namespace f32k;
 
-// A/B switches for timing builds (build variant "stamps+P32_BALANCE=0" etc.): the LDS-resident K
-// step shared out over the waves (1) or carried whole by wave 0 (0); running f64 Adam bias
-// corrections (1) or two fp32 pow() per step (0)
-#ifndef P32_BALANCE
-#define P32_BALANCE 0  // measured: 489-492 vs 492-497 rounds/s (profiles/r3d_mlp_ab), not kept on
-#endif
-#ifndef P32_RUNNING_BC
-#define P32_RUNNING_BC 1
-#endif
-// LL (value, tag) hand-offs (1) or write-through stores + drained flag (0), per hand-off
-#ifndef P32_LL_H1
-#define P32_LL_H1 0
-#endif
-// scheduling fences between the K steps of the forward / of C2 (1) or free interleaving (0).
-// Measured (profiles/r3h_sched): C2 unfenced 532.6 / 535.0 vs 512.1 / 521.8 rounds/s fenced, no
-// spills; the forward's fence is neutral and stays
-#ifndef P32_SB_FWD
-#define P32_SB_FWD 1
-#endif
-#ifndef P32_SB_C2
-#define P32_SB_C2 0
-#endif
-#ifndef P32_LL_PL
-#define P32_LL_PL 0
-#endif
-// heads' log-softmax over 2 x MT waves, two rows per lane (1), or MT waves, four rows per lane (0):
-// the per-row DPP reductions and exp / log chains are the critical path between the partial-logit
-// hand-off and dH2; the sums over the heads are taken in the same order either way (same bits)
-#ifndef P32_SM8
-#define P32_SM8 1
-#endif
-// heads' softmax chain shortened (1): v_exp / v_log (__expf / __logf, within 2 ulp) instead of the
-// range-reduced library expf / logf, the class probability as e / Σe (no second exp), and the
-// argmax's DPP reduction (accuracy metric only) moved behind the dH2 publish; 0: library exp / log,
-// p = exp(logp), argmax inline. Measured (profiles/r6t_fastsm): softmax 1.16 -> 0.92 us, 626.4 /
-// 627.4 / 628.0 vs 615.8 / 614.0 / 615.6 rounds/s
-#ifndef P32_FASTSM
-#define P32_FASTSM 1
-#endif
-// heads' H2 = H1 · W2ᵀ on the bf16 MFMA with both fp32 operands split exactly into three bf16
-// terms, six products kept (1), or on v_mfma_f32_16x16x4_f32 (0). Measured and not kept
-// (profiles/r6u_h2bf): the split of H1 per K slice costs more VALU than the MFMA time it saves,
-// H2 + partial logits 1.64 -> 1.96 us, 621.1 / 620.3 / 622.5 vs 626.8 / 626.3 / 629.5 rounds/s
-#ifndef P32_H2BF
-#define P32_H2BF 0
-#endif
-// direct-X epochs (layout 1, opt-in build -DP32_XDIRECT=1): batch rows read from the static bf16 copy
-// of the peer's images through the epoch index (MLPArgs::Xp16 / xidx, written by mlp_index_epoch)
-// instead of a per-epoch gathered copy. Measured slower (profiles/r4p_direct_x): the round boundary
-// loses the gather (an 8 x 7.5k index kernel replaces it) but C2's next-batch staging now waits on
-// the row index before its loads, 3.72 -> 4.28 us per step (519.4 / 524.8 vs 532.2 / 532.4
-// rounds/s). The engine asks mlp_persistent_f32_x_direct() which one the build expects.
-#ifndef P32_XDIRECT
-#define P32_XDIRECT 0
-#endif
-#ifndef P32_LDT_PAD
-#define P32_LDT_PAD 16
-#endif
-// swizzled X tile (xsw; 0: row stride kh * 32 + 8, no swizzle). Measured (profiles/r5_xswz): LDS bank
-// conflicts per LDS instruction 2.89 -> 1.10, but 8.6 % more LDS instructions, 256 VGPRs, and the
-// epoch 2 % longer (581.5 / 585.8 / 589.7 vs 580.4 / 594.1 / 594.0 rounds/s): kept off
-#ifndef P32_XSWZ
-#define P32_XSWZ 0
-#endif
-constexpr int SMR = (P32_SM8 && !P32_LL_PL) ? 2 : 4;  // softmax rows per lane
-#ifndef P32_LL_DH2
-#define P32_LL_DH2 0
-#endif
-constexpr int H1W = P32_LL_H1 ? 2 : 1;  // floats per H1 exchange element (value, tag)
+// Experiments this file carried as build-time switches, each measured and not kept; their code last
+// existed in commit f8de7cf:
+//   * LDS-resident K step shared out over two waves: 489-492 vs 492-497 rounds/s (profiles/r3d_mlp_ab).
+//   * two fp32 pow() per step instead of persist::BiasCorr: ~150 more VALU instructions per step.
+//   * LL (value, tag) pairs instead of the flag hand-offs (H1, partial logits, dH2): 524.9-589.4 vs
+//     598.5 / 600.9 rounds/s (profiles/r5_ll, r3e_ll_ab; dH2 across XCDs: profiles/r6_xr/ll_dh2).
+//   * a scheduling fence between C2's K steps: 512.1 / 521.8 vs 532.6 / 535.0 rounds/s unfenced
+//     (profiles/r3h_sched); the forward's fence is neutral (profiles/r5_ll) and stays.
+//   * heads' H2 on the bf16 MFMA, both operands split into three bf16 terms: H2 + partial logits
+//     1.64 -> 1.96 us, 621.1 / 620.3 / 622.5 vs 626.8 / 626.3 / 629.5 rounds/s (profiles/r6u_h2bf).
+//   * direct-X epochs (rows read through an epoch index from a static bf16 copy of the images): C2
+//     3.72 -> 4.28 us, 519.4 / 524.8 vs 532.2 / 532.4 rounds/s (profiles/r4p_direct_x).
+//   * swizzled X tile: bank conflicts 2.89 -> 1.10 per LDS instruction, but 8.6 % more of them, 256
+//     VGPRs, 581.5 / 585.8 / 589.7 vs 580.4 / 594.1 / 594.0 rounds/s (profiles/r5_xswz).
+//   * heads' softmax on library expf / logf, p = exp(logp), argmax inline: softmax 1.16 vs 0.92 us,
+//     615.8 / 614.0 / 615.6 vs 626.4 / 627.4 / 628.0 rounds/s (profiles/r6t_fastsm). The chain kept:
+//     v_exp / v_log (__expf / __logf, within 2 ulp), p = e / Σe, the argmax behind the dH2 publish.
+//
+// heads' log-softmax over 2 x MT waves, two rows per lane (MT waves with four rows each: 519.9 / 522.5
+// vs 529.8 / 530.6 rounds/s, profiles/r4g_softmax8): the per-row DPP reductions and exp / log chains
+// are the critical path between the partial-logit hand-off and dH2; the sums over the heads are taken
+// in the same order either way (same bits)
+constexpr int SMR = 2;  // softmax rows per lane
+// dH1 split tiles: row stride Bpad + LDT_PAD bf16 (owner_lds32; Bpad + 8, the old stride, left 2-way
+// conflicts: 601.4 / 600.7 / 599.9 vs 604.6 / 603.4 / 602.8 rounds/s, profiles/r5_ldt)
+constexpr int LDT_PAD = 16;
 // The next step's forward accumulated inside C2 (owner32's FUSE; docs/PERFORMANCE.md "Fused next-step
 // forward", profiles/r7_fwd_fuse). An early attempt lost on registers: 16.8 us/step vs 15.7,
 // C2 4.6 -> 6.6 us, 14 more VGPR spills. Now: the bench instantiation <64, Adam> holds the 16
@@ -273,26 +230,18 @@ constexpr int KS1_MAX = 25;  // K steps of 32 over D0 + the bias column: D0 <= 7
 // a sibling cannot publish step t + 2's before this owner published t + 1's (the heads' dH2(t + 1)
 // needs this group's reduced slice of t + 1), which it does only after reading step t's.
 __device__ __forceinline__ float* h1x_part(const MLPPersistF32Bufs& pb, int p, int kh, int t, int BP) {
-  return pb.h1x + (((int64_t)p * KSLAB + kh) * 2 + (t & 1)) * BP * PD1 * H1W;
+  return pb.h1x + (((int64_t)p * KSLAB + kh) * 2 + (t & 1)) * BP * PD1;
 }
 __device__ __forceinline__ float* h1x_red(const MLPPersistF32Bufs& pb, int p, int t, int BP) { return h1x_part(pb, p, KSMAX, t, BP); }
 
 
-// X tile chunk swizzle: within each K step's 32 columns, 16-byte chunk c of row r is stored at chunk
-// c ^ ((r >> 2) & 3). Every access (staging stores, zero fill, forward reads, C2's transposed reads)
-// goes through it; combined with the row stride of owner_lds32 it leaves no LDS bank conflicts on
-// the forward's and C2's reads (r5: the transposed reads were 2-way conflicted).
-__device__ __forceinline__ int xsw(int r, int col) {
-  return P32_XSWZ ? (col & ~31) | ((((col >> 3) & 3) ^ ((r >> 2) & 3)) << 3) | (col & 7) : col;
-}
-// frag_b_tr_l on the swizzled X tile: the B fragment of K rows k0.. (a multiple of 16) and the 16
-// columns n0 = 32 s + 16 tt of K step s
-// (k0 a multiple of 16: row r0 = k0 + 8g + q has swizzle 2(g & 1), row r0 + 4 that one with bit 0 set)
+// frag_b_tr_l on the X tile: the B fragment of K rows k0.. (a multiple of 16) and the 16 columns
+// n0 = 32 s + 16 tt of K step s
 __device__ __forceinline__ bf16x8 frag_b_tr_x(const bf16* base, int ld, int k0, int s, int tt, int lane) {
   const int g = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3;
-  const int cx = (2 * tt + (pp >> 1)) ^ (P32_XSWZ ? (g & 1) << 1 : 0);
+  const int cx = 2 * tt + (pp >> 1);
   const bf16* p0 = base + (k0 + 8 * g + q) * ld + 32 * s + (cx << 3) + 4 * (pp & 1);
-  const bf16* p1 = p0 + 4 * ld + (P32_XSWZ ? ((cx & 1) ? -8 : 8) : 0);
+  const bf16* p1 = p0 + 4 * ld;
   const mlp_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((mlp_lds_s16x4*)(p0));
   const mlp_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((mlp_lds_s16x4*)(p1));
   return __builtin_bit_cast(bf16x8, (mlp_s16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
@@ -302,20 +251,18 @@ __device__ __forceinline__ bf16x8 frag_b_tr_x(const bf16* base, int ld, int k0, 
 struct OwnerLds32 {
   int ldx;  // bf16 row stride of the X tile
   int ldt;  // bf16 row stride of the transposed dH1 split tiles [3][16][B]
-  size_t x, red, h1, dh1s, w1x, rows, ok, total;
+  size_t x, red, h1, dh1s, w1x, ok, total;
 };
 // K steps of one owner, at most: ceil(ks1 / KS) (kpart_begin splits them as evenly as possible)
 __host__ __device__ inline int kh_of(int D0, int KS) { return (ks1_of(D0) + KS - 1) / KS; }
 __host__ __device__ inline OwnerLds32 owner_lds32(int Bpad, int D0, int KS) {
   OwnerLds32 L;
-  // X tile rows of kh K steps, padded so the row stride is 4 (mod 16) 16-byte chunks: with the chunk
-  // swizzle xsw() both the forward's ds_read_b64 A reads and C2's ds_read_b64_tr_b16 reads are
-  // conflict-free (MI355X_MICROARCH.md §LDS lane groups; no pad at D0 = 784, K split 1 or 2)
-  L.ldx = kh_of(D0, KS) * 32 + (P32_XSWZ ? 8 * ((4 - 4 * kh_of(D0, KS)) & 15) : 8);
+  // X tile rows of kh K steps, one 16-byte chunk of padding per row
+  L.ldx = kh_of(D0, KS) * 32 + 8;
   // dH1 split tiles: row stride Bpad + 16 bf16 (80 / 48 at Bpad 64 / 32) puts the 16 rows x 4 column
   // chunks of C2's ds_read_b128 fragment reads on 16 distinct 4-bank slots in every lane group
-  // (MI355X_MICROARCH.md §LDS); Bpad + 8 left 2-way conflicts (P32_LDT_PAD=8: the old stride, A/B)
-  L.ldt = Bpad + P32_LDT_PAD;
+  // (MI355X_MICROARCH.md §LDS)
+  L.ldt = Bpad + LDT_PAD;
   const int MT = Bpad / 16;
   const size_t red = (size_t)8 * MT * 64 * 16, dh2 = (size_t)Bpad * LDD * 4;
   size_t o = 0;
@@ -324,7 +271,6 @@ __host__ __device__ inline OwnerLds32 owner_lds32(int Bpad, int D0, int KS) {
   L.h1 = o;   o += al16((size_t)2 * Bpad * 16 * 4);  // own H1 slice, step-parity double buffer
   L.dh1s = o; o += al16((size_t)3 * 16 * L.ldt * 2);  // dH1ᵀ as hi / mid / lo bf16 (exact split)
   L.w1x = o;  o += al16(KS == 1 ? (size_t)4 * 16 * 32 * 4 : 0);  // KS = 1: W1 state of K step 24 (w, m, v, e)
-  L.rows = o; o += al16((size_t)Bpad * 4);  // direct-X epochs: the next batch's sample indices
   L.ok = o;   o += 16;
   L.total = o;
   return L;
@@ -378,10 +324,10 @@ __device__ __forceinline__ bool gang_commit(const MLPArgs& a, const MLPPersistF3
 }
 
 template <int BP, bool ADAM, bool EXTRA, int KS, bool RH, bool FUSE = false>
-__device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, int g, char* smem, unsigned gen) {
+__device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, int g, char* smem) {
   // FUSE: the forward of step t + 1 is accumulated inside C2 of step t, K step by K step, by the wave
   // that has just updated that K step's weights and staged its columns of the next batch
-  static_assert(!FUSE || (KS == 1 && !RH && !EXTRA && !P32_LL_H1 && !P32_BALANCE && !P32_XSWZ), "fused forward: layout 1, K split 1, no extra term");
+  static_assert(!FUSE || (KS == 1 && !RH && !EXTRA), "fused forward: layout 1, K split 1, no extra term");
   constexpr int MT = BP / 16;
   constexpr int RQ = rq_of(KS);
   constexpr int XPT = BP / 4;  // 16-byte X chunks per lane: 4 K steps x BP rows x 4 chunks / 64 lanes
@@ -391,11 +337,6 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
   const int cg = g % NCG, kh = g / NCG;  // column group, K part
   const int D0 = a.D0;
   constexpr bool XR = xr_of(KS, RH);  // cross-XCD K split (see the constants above)
-  // dH2 as LL (value, tag) pairs: opt-in (P32_LL_DH2). Measured across XCDs too (XR, one peer at
-  // K split 8, profiles/r6_xr/ll_dh2): the heads' publish 0.80 -> 0.32 us, the owners' load of the
-  // doubled payload 1.60 -> 2.10 us, the step 12.36 -> 12.52 us (627.8 vs 628.8 rounds/s): kept off
-  constexpr bool LLD = P32_LL_DH2;
-  static_assert(!(XR && P32_LL_H1), "the cross-XCD K split uses flag hand-offs for H1");
   const int s0 = kpart_begin(ks1_of(D0), KS, kh);  // first (global) K step of this owner; local K step j is global s0 + j
   const int KS1 = kpart_begin(ks1_of(D0), KS, kh + 1) - s0;  // local K steps of this owner (<= kh_of(D0, KS))
   const int C0 = 32 * s0;  // first global X column of the tile
@@ -407,14 +348,7 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
   float* sH1 = reinterpret_cast<float*>(smem + L.h1);
   bf16* sD3 = reinterpret_cast<bf16*>(smem + L.dh1s);  // [hi, mid, lo][o1 local][b]
   float* sW1x = reinterpret_cast<float*>(smem + L.w1x);  // [w, m, v, e][16][32]: K step 24
-  int* sRowN = reinterpret_cast<int*>(smem + L.rows);     // direct X: sample index of next-batch row r
   int* sOk = reinterpret_cast<int*>(smem + L.ok);
-  // direct-X epoch (a.x_direct): batch row r of step t is image xidx[p][tB + r] of the peer's static
-  // bf16 copy (no per-epoch gather of the images; the index kernel wrote xidx)
-  constexpr bool xd = P32_XDIRECT != 0;
-  const bf16* xp16 = xd ? a.Xp16[p] : nullptr;
-  const int* xidx_p = xd ? a.xidx + (int64_t)p * a.xb_rows : nullptr;
-
   const OptParams& o = a.opt;
   const int4 ctl = a.ctl[p];
   const bool fresh = (ctl.x & 2) != 0;
@@ -496,11 +430,10 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
       const int idx = kk * 64 + lv;
       const int r = idx >> 2, col = 32 * s + 8 * (idx & 3), gcol = C0 + col;
       if (s < KS1 && gcol < D0) {
-        const bf16* src = xd ? (r < rows ? xp16 + (int64_t)xidx_p[t * a.B + r] * D0 + gcol : xp16)
-                             : a.Xb16 + ((int64_t)p * a.xb_rows + (int64_t)t * a.B + r) * D0 + gcol;
-        *reinterpret_cast<uint4*>(sX + r * LDX + xsw(r, col)) = r < rows ? *reinterpret_cast<const uint4*>(src) : uint4{0u, 0u, 0u, 0u};
+        const bf16* src = a.Xb16 + ((int64_t)p * a.xb_rows + (int64_t)t * a.B + r) * D0 + gcol;
+        *reinterpret_cast<uint4*>(sX + r * LDX + col) = r < rows ? *reinterpret_cast<const uint4*>(src) : uint4{0u, 0u, 0u, 0u};
       } else if (s < KS1 && gcol == D0) {
-        *reinterpret_cast<uint4*>(sX + r * LDX + xsw(r, col)) = bias_chunk(r < rows);
+        *reinterpret_cast<uint4*>(sX + r * LDX + col) = bias_chunk(r < rows);
       }
     }
   };
@@ -509,7 +442,7 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
     if (z0 < z1)
       for (int e = tid; e < BP * (z1 - z0); e += NT) {
         const int r = e / (z1 - z0), q = e % (z1 - z0);
-        sX[r * LDX + xsw(r, z0 + q)] = (bf16)0.f;
+        sX[r * LDX + (z0 + q)] = (bf16)0.f;
       }
   }
   if (nsteps > 0) xw_stage(0, lane);
@@ -517,17 +450,16 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
   // deferred W2-replica update of step tp: dW2[o2][16g + c] over the batch, with dH2(tp) re-read
   // (sc1) from the step-parity buffer and H1(tp) from this workgroup's LDS
   auto w2_replica_update = [&](int tp, float lr_p, float inv_p) {
-    // dH2(tp): LL pairs, verified at step tp; read through a buffer resource with 32-bit offsets from
-    // a laundered lane (64-bit per-kb addresses hoisted out of the step loop would be spilled)
-    constexpr int DW = LLD ? 2 : 1;  // floats per dH2 exchange element
+    // dH2(tp), read through a buffer resource with 32-bit offsets from a laundered lane (64-bit
+    // per-kb addresses hoisted out of the step loop would be spilled)
     const __amdgpu_buffer_rsrc_t rd = rsrc_of(pb.dh2x + ((int64_t)p * 2 + (tp & 1)) * BP * PD2 * 2, BP * PD2 * 8);
     int lr = lane;
     asm volatile("" : "+v"(lr));
-    const int ro = 4 * DW * ((lr >> 4) * PD2 + 16 * wave + (lr & 15));
+    const int ro = 4 * ((lr >> 4) * PD2 + 16 * wave + (lr & 15));
     const float* h1p = sH1 + (tp & 1) * BP * 16;
     float av[BP / 4];
 #pragma unroll
-    for (int kb = 0; kb < BP / 4; ++kb) av[kb] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rd, ro + 4 * DW * 4 * kb * PD2, 0, 16));
+    for (int kb = 0; kb < BP / 4; ++kb) av[kb] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rd, ro + 4 * 4 * kb * PD2, 0, 16));
     f32x4 acc = zero4();
 #pragma unroll
     for (int kb = 0; kb < BP / 4; ++kb) acc = mfma_f32(av[kb], h1p[(4 * kb + h) * 16 + c], acc);
@@ -536,12 +468,10 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
   };
   // forward contribution of this wave's K step q (slot q) to the H1 slice, with the weights as they
   // are now and the batch tile currently staged in LDS. The LDS-resident K step (q == RQ, KS = 1:
-  // K step 24, D0 > 767) is shared out by batch tile: wave w < MT adds only tile mt = w, so no wave
-  // carries a fourth whole K step (it made wave 0 the critical path of the forward).
+  // K step 24, D0 > 767) is wave 0's.
   auto fwd_kstep = [&](int q, f32x4(&acc)[MT]) {
-    const bool lds_step = P32_BALANCE && KS == 1 && q == RQ;
-    const int s = lds_step ? 8 * RQ : wave + 8 * q;
-    if (s >= KS1 || (lds_step && wave >= MT)) return;
+    const int s = wave + 8 * q;
+    if (s >= KS1) return;
     // lane coordinates laundered per K step: the compiler would otherwise hoist every LDS address
     // of the loop out of it and spill them
     int lq = lane;
@@ -572,11 +502,8 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
     }
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
-      if (lds_step && mt != wave) continue;  // wave-uniform
-      const int xs = P32_XSWZ ? cq >> 2 : 0;  // xsw of row 16mt + cq: swizzled chunks of columns 4hq.. and 16 + 4hq..
       const bf16* xp = sX + (16 * mt + cq) * LDX + 32 * s + 4 * (hq & 1);
-      const bf16x8 af = cat8(*reinterpret_cast<const bf16x4*>(xp + (((hq >> 1) ^ xs) << 3)),
-                             *reinterpret_cast<const bf16x4*>(xp + (((2 + (hq >> 1)) ^ xs) << 3)));
+      const bf16x8 af = cat8(*reinterpret_cast<const bf16x4*>(xp + ((hq >> 1) << 3)), *reinterpret_cast<const bf16x4*>(xp + ((2 + (hq >> 1)) << 3)));
       acc[mt] = mfma3(af, bh, bm, bl, acc[mt]);
     }
   };
@@ -587,7 +514,7 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
 #pragma unroll
     for (int q = 0; q < (KS == 1 ? RQ + 1 : RQ); ++q) {
       fwd_kstep(q, acc);
-      if (P32_SB_FWD) __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_sched_barrier(0);
     }
   };
   // H1(t) from the waves' partial sums: cross-wave reduction in wave order 0..7, relu, rows past the
@@ -612,17 +539,11 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
         // b1 came in through the bias column; KS > 1: a partial sum (relu after the kh-ordered sum)
         const float v = b < rows ? (KS == 1 ? fmaxf(s[i], 0.f) : s[i]) : 0.f;
         sH1c[b * 16 + cc] = v;
-#if P32_LL_H1
-        persist::ll_st1p(pb.plain, h1x_part(pb, p, kh, t, BP) + 2 * ((int64_t)b * PD1 + NCG * cg + cc), v, persist::ll_tag(gen, pb.fbase, t));
-#else
         persist::pub32(pb.plain, h1x_part(pb, p, kh, t, BP) + (unsigned)(b * PD1 + NCG * cg + cc), v);
-#endif
       }
     }
     if (g == 0) P32_STAMP(0, t, 1);
-#if !P32_LL_H1
     persist::publish_p(pb.flags, FPP, p, XR ? F_H1P + cg * KS + kh : F_H1 + g, pb.fbase + (unsigned)(t + 1), pb.plain);
-#endif
     if (XR) {
       // the column group's KS partials, all on this XCD (plain when the placement check passed):
       // summed in kh order and relu'd by every owner of the group (same bits in each); K part 0
@@ -655,7 +576,10 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
     if (g == 0) P32_STAMP(0, t, 2);
     return true;
   };
-  if (tid == 0) sOk[1] = 1;  // LL bulk-load verdict (0: a wave gave up)
+  // sOk[1] is always 1: it was the LL bulk-load verdict, and no path clears it any more. The word and
+  // its read after the dH2 load stay because the bench instantiation <64, Adam, fused> spills 5 VGPRs
+  // (24 B of scratch) without that read; head32 keeps its pair for speed (profiles/r8_strip_switches)
+  if (tid == 0) sOk[1] = 1;
   __syncthreads();  // sW1x written
 
   if (FUSE && nsteps > 0) {  // H1(0); every later H1(t + 1) comes out of step t's C2
@@ -671,12 +595,8 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
     int tv = tid;  // per-iteration opaque thread index (addresses re-derived each step: VGPR pressure)
     asm volatile("" : "+v"(tv));
     const float lr_prev = lr_t, inv_prev = inv_bc2;  // step t - 1 (the deferred W2-replica update)
-    const unsigned tag = persist::ll_tag(gen, pb.fbase, t);
-#if P32_RUNNING_BC
+    const unsigned t1 = (unsigned)(t + 1);  // this step's flag value, less fbase
     bc.next(o, lr_t, inv_bc2);
-#else
-    persist::bias_corr(o, ctl.z, t, lr_t, inv_bc2);
-#endif
     float* sH1c = sH1 + (t & 1) * BP * 16;
     if (g == 0) P32_STAMP(0, t, 0);
 
@@ -699,17 +619,9 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
     if (more) {
       const int rows_n = rows_at(a, n, t + 1);
       unsigned sink = 0;
-      // direct X: this lane's next-batch row (lane < BP) through the epoch index; wave 0 leaves the
-      // indices in LDS for C2's staging (read after the dH2 barriers below)
-      int xi = lane;
+      int xi = lane;  // this lane's next-batch row
       if (FUSE) asm volatile("" : "+v"(xi));  // (a hoisted 64-bit row address was spilled)
-      if (xd) {
-        xi = (lane < rows_n && lane < BP) ? xidx_p[(t + 1) * a.B + lane] : 0;
-        int ln = lane;  // laundered: a hoisted LDS address was the bench instantiation's one VGPR spill
-        asm volatile("" : "+v"(ln));
-        if (wave == 0 && ln < BP) sRowN[ln] = xi;
-      }
-      const bf16* xbase = xd ? xp16 : a.Xb16 + ((int64_t)p * a.xb_rows + (int64_t)(t + 1) * a.B) * D0;
+      const bf16* xbase = a.Xb16 + ((int64_t)p * a.xb_rows + (int64_t)(t + 1) * a.B) * D0;
       const bf16* xrow = xbase + (unsigned)(xi * D0);
 #pragma unroll
       for (int q = 0; q < (KS == 1 ? RQ + 1 : RQ); ++q) {
@@ -727,8 +639,7 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
     // step q's chunks are stored, ahead of its forward, and K step 0's here, ahead of the dH2 wait:
     // their L2 latency runs under the wait and under the previous K step instead of in front of
     // every K step's store.
-    constexpr bool FUSEX = FUSE && !xd;
-    constexpr int XQF = FUSEX ? BP / 16 : 1;
+    constexpr int XQF = FUSE ? BP / 16 : 1;
     uint4 xqf[XQF];
     const __amdgpu_buffer_rsrc_t r_xn =
         rsrc_of(a.Xb16 + ((int64_t)p * a.xb_rows + (int64_t)(t + 1) * a.B) * D0, more ? rows_at(a, n, t + 1) * D0 * 2 : 0);
@@ -745,17 +656,12 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
         xqf[kk] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r_xn, off, 0, 0));
       }
     };
-    if constexpr (FUSEX) xq_load(0);
+    if constexpr (FUSE) xq_load(0);
 
     // ================= C: backward of this slice
     const float* dh2_t = pb.dh2x + ((int64_t)p * 2 + (t & 1)) * BP * PD2 * 2;
     const __amdgpu_buffer_rsrc_t r_dh2 = rsrc_of(dh2_t, BP * PD2 * 8);
-    if constexpr (LLD) {
-      // representative wait (one chunk per head: its first two columns of row 0), then the bulk load
-      if (!persist::ll_wg_wait([&](int k) { return persist::ll_ld2(r_dh2, 16 * k * 8); }, NH, tag, pb.err, sOk)) return;
-    } else {
-      if (!persist::wg_wait(pb.flags, FPP, p, RH ? F3_DH2 : F_DH2, RH ? nhr_of(BP) : NH, pb.fbase + (unsigned)(t + 1), pb.err, sOk)) return;
-    }
+    if (!persist::wg_wait(pb.flags, FPP, p, RH ? F3_DH2 : F_DH2, RH ? nhr_of(BP) : NH, pb.fbase + t1, pb.err, sOk)) return;
     if (g == 0) P32_STAMP(0, t, 4);
     if (KS > 1 && !XR) {
       // (layout 3) full H1 slice = the K parts' partials summed in kh order (the heads' order: same
@@ -769,16 +675,8 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
           if (k2 == kh) {
             v = *reinterpret_cast<const float4*>(sH1c + b * 16 + c4);
           } else {
-#if P32_LL_H1
-            const __amdgpu_buffer_rsrc_t r = rsrc_of(h1x_part(pb, p, k2, t, BP), BP * PD1 * 8);
-            persist::ll_u32x4 u2[2];
-            if (!persist::ll_wait(u2, [&](int k) { return persist::ll_ld2(r, 8 * (b * PD1 + NCG * cg + c4) + 16 * k); }, tag, pb.err)) sOk[1] = 0;
-            v = float4{__uint_as_float(u2[0][0]), __uint_as_float(u2[0][2]), __uint_as_float(u2[1][0]),
-                       __uint_as_float(u2[1][2])};
-#else
             const __amdgpu_buffer_rsrc_t r = rsrc_of(h1x_part(pb, p, k2, t, BP), BP * PD1 * 4);
             v = ld_sc1_16(r, (b * PD1 + NCG * cg + c4) * 4);
-#endif
           }
           sum.x += v.x;
           sum.y += v.y;
@@ -788,7 +686,7 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
         *reinterpret_cast<float4*>(sH1c + b * 16 + c4) = float4{fmaxf(sum.x, 0.f), fmaxf(sum.y, 0.f), fmaxf(sum.z, 0.f), fmaxf(sum.w, 0.f)};
       }
     }
-    if constexpr (!LLD) {
+    {
       float4 v[BP / 16];
 #pragma unroll
       for (int k = 0; k < BP / 16; ++k) v[k] = ld_sc1_16(r_dh2, (tv + NT * k) * 16);  // BP x 128 fp32 = BP*32 chunks
@@ -797,19 +695,9 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
         const int e = tv + NT * k;
         *reinterpret_cast<float4*>(sDH2 + (e >> 5) * LDD + 4 * (e & 31)) = v[k];
       }
-    } else {
-      // BP x 128 LL pairs = BP*64 16-byte chunks (2 columns each), every tag verified
-      persist::ll_u32x4 v[BP / 8];
-      const bool ok = persist::ll_wait(v, [&](int k) { return persist::ll_ld2(r_dh2, (tv + NT * k) * 16); }, tag, pb.err);
-#pragma unroll
-      for (int k = 0; k < BP / 8; ++k) {
-        const int e = tv + NT * k;
-        *reinterpret_cast<float2*>(sDH2 + (e >> 6) * LDD + 2 * (e & 63)) = float2{__uint_as_float(v[k][0]), __uint_as_float(v[k][2])};
-      }
-      if (!ok) sOk[1] = 0;
     }
     lds_barrier();
-    if (sOk[1] == 0) return;
+    if (sOk[1] == 0) return;  // (never taken: see sOk[1] above)
     // C1: dH1 partials — wave w sums its 16 o2 rows (k order o2 = 16w + 4h + ks)
     {
       f32x4 acc1[MT];
@@ -882,51 +770,33 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
 #pragma unroll
       for (int mt = 0; mt < (FUSE ? MT : 1); ++mt) accF[mt] = zero4();
       const int rows_next = more ? rows_at(a, n, t + 1) : 0;
-      const bf16* xnext = xd ? xp16 : a.Xb16 + ((int64_t)p * a.xb_rows + (int64_t)(t + 1) * a.B) * D0;
+      const bf16* xnext = a.Xb16 + ((int64_t)p * a.xb_rows + (int64_t)(t + 1) * a.B) * D0;
 #pragma unroll
       for (int q = 0; q < (KS == 1 ? RQ + 1 : RQ); ++q) {
-        // register K steps: wave w owns K step w + 8q, both 16-column halves (tt = 0, 1). The
-        // LDS-resident K step (q == RQ, KS = 1) is shared out by half: wave NW-2 takes tt = 0
-        // (columns 768..783), wave NW-1 tt = 1 (the bias column and padding) — each reads, updates
-        // and restages only its own half of the tile, so the halves never race.
-        const bool lds_step = P32_BALANCE && KS == 1 && q == RQ;
-        constexpr int NW = NT / 64;
-        const int s = lds_step ? 8 * RQ : wave + 8 * q;
-        const int tt_lo = lds_step ? wave - (NW - 2) : 0;
-        const int tt_hi = lds_step ? tt_lo + 1 : 2;
-        if (P32_SB_C2) __builtin_amdgcn_sched_barrier(0);
-        if (s < KS1 && tt_lo >= 0) {
+        // wave w owns K step w + 8q, both 16-column halves (tt = 0, 1); q == RQ (KS = 1): the
+        // LDS-resident K step, wave 0's
+        const int s = wave + 8 * q;
+        if (s < KS1) {
           int lq = lane;
           asm volatile("" : "+v"(lq));
           const bf16* dfrag = sD3 + (lq & 15) * LDT + 8 * (lq >> 4);
           constexpr int XQ = BP / 16;
           // this lane's 16-byte chunks of the K step: chunk (lv & 3) of a row covers columns
-          // 32s + 8(lv & 3) .. +8, i.e. half tt = (lv & 3) >> 1
-          const bool xmine = !lds_step || ((lv & 3) >> 1) == tt_lo;
+          // 32s + 8(lv & 3) .. +8
           uint4 xq[XQ];
 #pragma unroll
           for (int kk = 0; kk < XQ; ++kk) {
-            if constexpr (FUSEX) {  // loaded ahead (xq_load)
-              xq[kk] = xqf[FUSEX ? kk : 0];
+            if constexpr (FUSE) {  // loaded ahead (xq_load)
+              xq[kk] = xqf[FUSE ? kk : 0];
               continue;
             }
             const int idx = kk * 64 + lv;
             const int r = idx >> 2, col = 32 * s + 8 * (idx & 3), gcol = C0 + col;
-#ifdef P32_EXP_NOX  // timing experiment: no next-batch staging loads
-            xq[kk] = uint4{(unsigned)lv, 0u, 0u, 0u};
-#else
-            const bool xl = more && xmine && gcol < D0 && r < rows_next;
-            // row of the next batch: static-copy image (direct X; re-read from LDS per K step — four
-            // indices held across C2 cost the bench instantiation a VGPR spill) or batch row
-            int rr = r;
-            if (xd) asm volatile("" : "+v"(rr));
-            const int rid = xd ? sRowN[rr] : r;
-            xq[kk] = xl ? *reinterpret_cast<const uint4*>(xnext + (unsigned)(rid * D0 + gcol)) : uint4{0u, 0u, 0u, 0u};
-#endif
+            const bool xl = more && gcol < D0 && r < rows_next;
+            xq[kk] = xl ? *reinterpret_cast<const uint4*>(xnext + (unsigned)(r * D0 + gcol)) : uint4{0u, 0u, 0u, 0u};
           }
 #pragma unroll
           for (int tt = 0; tt < 2; ++tt) {
-            if (tt < tt_lo || tt >= tt_hi) continue;  // wave-uniform
             f32x4 acc = zero4();  // C[k = 32s + 16tt + 4h + i][o1 = c]
 #pragma unroll
             for (int kb = 0; kb < BP / 32; ++kb)
@@ -934,14 +804,9 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
                           ld8(dfrag + 32 * LDT + 32 * kb), acc);
             if (q < RQ) {
               const int qq = q < RQ ? q : 0;
-#ifdef P32_EXP_NOADAM  // timing experiment: plain SGD in place of the Adam epilogue
-#pragma unroll
-              for (int i = 0; i < 4; ++i) w1[qq][4 * tt + i] -= 1e-9f * acc[i];
-#else
 #pragma unroll
               for (int i = 0; i < 4; ++i)
                 upd32<ADAM, EXTRA>(o, acc[i], w1[qq][4 * tt + i], m1[qq][4 * tt + i], v1[qq][4 * tt + i], e1[qq][4 * tt + i], lr_t, inv_bc2, wdmu);
-#endif
             } else {  // the LDS-resident K step
               const int off = (lq & 15) * 32 + 16 * tt + 4 * (lq >> 4);
               float4 w = *reinterpret_cast<float4*>(sW1x + off), m = *reinterpret_cast<float4*>(sW1x + 512 + off),
@@ -960,20 +825,17 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
             for (int kk = 0; kk < XQ; ++kk) {
               const int idx = kk * 64 + lv;
               const int r = idx >> 2, col = 32 * s + 8 * (idx & 3), gcol = C0 + col;
-              if (!xmine) continue;
               if (gcol < D0)
-                *reinterpret_cast<uint4*>(sX + r * LDX + xsw(r, col)) = xq[kk];
+                *reinterpret_cast<uint4*>(sX + r * LDX + col) = xq[kk];
               else if (gcol == D0)
-                *reinterpret_cast<uint4*>(sX + r * LDX + xsw(r, col)) = bias_chunk(r < rows_next);
+                *reinterpret_cast<uint4*>(sX + r * LDX + col) = bias_chunk(r < rows_next);
             }
           }
         }
         // fused loop: the K step's weights are updated and its columns of X(t + 1) staged, both by
         // this wave (its own registers and LDS writes, which complete in order): no barrier
         if constexpr (FUSE) {
-          if constexpr (FUSEX) {
-            if (q + 1 < (KS == 1 ? RQ + 1 : RQ)) xq_load(q + 1);
-          }
+          if (q + 1 < (KS == 1 ? RQ + 1 : RQ)) xq_load(q + 1);
           if (more) fwd_kstep(q, accF);
         }
       }
@@ -1058,11 +920,9 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
 // head workgroup
 // =============================================================================================
 template <int BP, bool ADAM, bool EXTRA, int KS>
-__device__ void head32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, int hd, char* smem, unsigned gen) {
+__device__ void head32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, int hd, char* smem) {
   constexpr int MT = BP / 16;
   constexpr bool XR = xr_of(KS, false);
-  static_assert(!(XR && P32_LL_H1), "the cross-XCD K split uses flag hand-offs for H1");
-  constexpr bool LLD = P32_LL_DH2;  // dH2 as LL pairs (owner32)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int h = lane >> 4, c = lane & 15;
@@ -1140,7 +1000,10 @@ __device__ void head32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, int
     sB3[32 + k] = (kin && ADAM && !fresh) ? a.v[idx] : 0.f;
     sB3[48 + k] = (kin && EXTRA) ? extra_at(a, idx) : 0.f;
   }
-  if (tid == 0) sOk[1] = 1;  // LL verdict (0: a wave gave up)
+  // sOk[1] is always 1 (it was the LL verdict; no path clears it any more). The word and its read
+  // after the softmax stay: without them the headline ran 0.7 % slower, 680.5-682.8 vs 684.8-687.2
+  // rounds/s (profiles/r8_strip_switches)
+  if (tid == 0) sOk[1] = 1;
   __syncthreads();
   float loss_acc = 0.f, correct_acc = 0.f;
 
@@ -1151,23 +1014,17 @@ __device__ void head32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, int
     asm volatile("" : "+v"(tv));
     const int rows = rows_at(a, n, t);
     float lr_t, inv_bc2;
-#if P32_RUNNING_BC
     bc.next(o, lr_t, inv_bc2);
-#else
-    persist::bias_corr(o, ctl.z, t, lr_t, inv_bc2);
-#endif
-    const unsigned tag = persist::ll_tag(gen, pb.fbase, t);
+    const unsigned target = pb.fbase + (unsigned)(t + 1);  // this step's flag value
 
     // labels of this lane's softmax rows, loaded before the waits (off the critical path)
     // softmax wave w: rows 16 (w / (4 / SMR)) + 4h + SMR (w % (4 / SMR)) + i, i < SMR
     constexpr int SMW = MT * (4 / SMR);  // softmax waves
     const int sm_mt = wave / (4 / SMR), sm_i0 = SMR * (wave % (4 / SMR));
     int yv[SMR];
-#if P32_FASTSM
     int cand_v[SMR];
 #pragma unroll
     for (int i = 0; i < SMR; ++i) cand_v[i] = 16;
-#endif
 #pragma unroll
     for (int i = 0; i < SMR; ++i) yv[i] = -1;
     if (wave < SMW) {
@@ -1180,40 +1037,9 @@ __device__ void head32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, int
     // ---- H1(t) from the owners -> LDS (16-byte sc1 loads); KS > 1: the K parts' partials summed
     //      in kh order (the owners' order: same bits), then relu
     if (hd == 0) P32_STAMP(1, t, 0);
-#if P32_LL_H1
-    {
-      // representative wait: lane k polls owner k's first two columns of row 0 (K part k / NCG)
-      const __amdgpu_buffer_rsrc_t r_all = rsrc_of(h1x_part(pb, p, 0, t, BP), KSMAX * 2 * BP * PD1 * 8);
-      if (!persist::ll_wg_wait([&](int k) { return persist::ll_ld2(r_all, ((k / NCG) * 2 * BP * PD1 + NCG * (k % NCG)) * 8); }, ng_of(KS), tag, pb.err, sOk))
-        return;
-    }
-    if (hd == 0) P32_STAMP(1, t, 1);
-    {
-      // BP x 256 pairs per K part = BP*128 chunks of 2 columns; parts summed in kh order
-      float2 sum[BP / 4];
-#pragma unroll
-      for (int k2 = 0; k2 < KS; ++k2) {
-        const __amdgpu_buffer_rsrc_t r = rsrc_of(h1x_part(pb, p, k2, t, BP), BP * PD1 * 8);
-        persist::ll_u32x4 u[BP / 4];
-        if (!persist::ll_wait(u, [&](int k) { return persist::ll_ld2(r, (tv + NT * k) * 16); }, tag, pb.err)) sOk[1] = 0;
-#pragma unroll
-        for (int k = 0; k < BP / 4; ++k) {
-          const float2 v = {__uint_as_float(u[k][0]), __uint_as_float(u[k][2])};
-          sum[k] = k2 == 0 ? v : float2{sum[k].x + v.x, sum[k].y + v.y};
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < BP / 4; ++k) {
-        float2 v = sum[k];
-        if (KS > 1) v = float2{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f)};
-        const int e = tv + NT * k;
-        *reinterpret_cast<float2*>(sH1 + (e >> 7) * LDH1 + 2 * (e & 127)) = v;
-      }
-    }
-#else
     // XR: the owners reduced the K parts; the heads read one slice per column group, as at KS = 1
     constexpr int KSR = XR ? 1 : KS;
-    if (!persist::wg_wait(pb.flags, FPP, p, F_H1, XR ? NCG : ng_of(KS), pb.fbase + (unsigned)(t + 1), pb.err, sOk)) return;
+    if (!persist::wg_wait(pb.flags, FPP, p, F_H1, XR ? NCG : ng_of(KS), target, pb.err, sOk)) return;
     if (hd == 0) P32_STAMP(1, t, 1);
     {
       // every partial's loads issued before any is consumed (one L2 round trip, not KS)
@@ -1239,45 +1065,13 @@ __device__ void head32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, int
         *reinterpret_cast<float4*>(sH1 + (e >> 6) * LDH1 + 4 * (e & 63)) = v;
       }
     }
-#endif
     lds_barrier();
-#if P32_LL_H1
-    if (sOk[1] == 0) return;
-#endif
     if (hd == 0) P32_STAMP(1, t, 2);
     // ---- H2 slice = relu(H1 · W2rowsᵀ + b2); wave w sums o1 in [32w, 32w+32) (k order 16g + 4h + i)
     {
       f32x4 acc[MT];
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) acc[mt] = zero4();
-#if P32_H2BF
-      // both fp32 operands split exactly into bf16 hi / mid / lo; six v_mfma_f32_16x16x32_bf16 terms
-      // replace eight f32 MFMAs per 32-wide K slice (the three dropped cross terms are below 2^-32
-      // of the product). K slot (h, j) of the bf16 fragment is o1 = 32w + 16(j / 4) + 4h + j % 4:
-      // exactly the eight W2 values this lane already holds (w2[j / 4][j % 4])
-      {
-        float wq[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) wq[j] = w2[j >> 2][j & 3];
-        bf16x8 bh, bm, bl;
-        split3(wq, bh, bm, bl);
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-          const float* hp = sH1 + (16 * mt + c) * LDH1 + 32 * wave + 4 * h;
-          const float4 a0 = *reinterpret_cast<const float4*>(hp);
-          const float4 a1 = *reinterpret_cast<const float4*>(hp + 16);
-          const float aq[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-          bf16x8 ah, am, al;
-          split3(aq, ah, am, al);
-          f32x4 t = mfma_bf16(al, bh, acc[mt]);  // smallest terms first
-          t = mfma_bf16(ah, bl, t);
-          t = mfma_bf16(am, bm, t);
-          t = mfma_bf16(am, bh, t);
-          t = mfma_bf16(ah, bm, t);
-          acc[mt] = mfma_bf16(ah, bh, t);
-        }
-      }
-#else
 #pragma unroll
       for (int gg = 0; gg < 2; ++gg) {
         const int g = 2 * wave + gg;
@@ -1290,7 +1084,6 @@ __device__ void head32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, int
           acc[mt] = mfma_f32(av.w, w2[gg][3], acc[mt]);
         }
       }
-#endif
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) sRed[(wave * MT + mt) * 64 + lane] = acc[mt];
     }
@@ -1316,69 +1109,30 @@ __device__ void head32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, int
       pl = mfma_f32(av.y, bv.y, pl);
       pl = mfma_f32(av.z, bv.z, pl);
       pl = mfma_f32(av.w, bv.w, pl);
-      // plx[p][hd][wave][lane] = 4 partial logits (rows 16·wave + 4h + i, class c) as two LL pair
-      // chunks: the consuming lane of every head has the same (wave, h, c) and reads its four rows
-#if P32_LL_PL
-      persist::ll_st2p(pb.plain, pb.plx + ((int64_t)p * NH + hd) * BP * 16 * 2, BP * 16 * 8, (wave * 64 + lane) * 32, pl[0], pl[1], tag);
-      persist::ll_st2p(pb.plain, pb.plx + ((int64_t)p * NH + hd) * BP * 16 * 2, BP * 16 * 8, (wave * 64 + lane) * 32 + 16, pl[2], pl[3], tag);
-#else
+      // plx[p][hd][wave][lane] = 4 partial logits (rows 16·wave + 4h + i, class c): the consuming
+      // lanes of every head have the same (wave, h, c) and read their rows of the four
       persist::pub128(pb.plain, pb.plx + ((int64_t)p * NH + hd) * BP * 16 * 2, BP * 16 * 4, (wave * 64 + lane) * 16, __builtin_bit_cast(u32x4, pl));
-#endif
     }
     if (hd == 0) P32_STAMP(1, t, 3);
-#if !P32_LL_PL
-    persist::publish_p(pb.flags, FPP, p, F_PL + hd, pb.fbase + (unsigned)(t + 1), pb.plain);
-    if (!persist::wg_wait(pb.flags, FPP, p, F_PL, NH, pb.fbase + (unsigned)(t + 1), pb.err, sOk)) return;
-#endif
+    persist::publish_p(pb.flags, FPP, p, F_PL + hd, target, pb.plain);
+    if (!persist::wg_wait(pb.flags, FPP, p, F_PL, NH, target, pb.err, sOk)) return;
     if (hd == 0) P32_STAMP(1, t, 4);
 
     // ---- logits = Σ_heads partials (fixed order: every head gets the same bits) + b3, straight
-    //      into the softmax lanes' registers; each softmax wave polls its own LL chunks
+    //      into the softmax lanes' registers
     // ---- log-softmax + NLL + argmax + dlogits of the whole batch (wave w < MT: rows 16w..)
     if (wave < SMW) {
       float lsum[SMR];
-#if P32_LL_PL
-      const __amdgpu_buffer_rsrc_t r = rsrc_of(pb.plx + (int64_t)p * NH * BP * 16 * 2, NH * BP * 16 * 8);
-      persist::ll_u32x4 u[2 * NH];
-      const bool ok = persist::ll_wait(u, [&](int k) { return persist::ll_ld2(r, (k >> 1) * BP * 16 * 8 + (wave * 64 + lane) * 32 + (k & 1) * 16); }, tag, pb.err);
-      if (!ok) sOk[1] = 0;
-      if (hd == 0) P32_STAMP(1, t, 5);
-      float4 sl = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int k = 0; k < NH; ++k) {
-        const float4 vk = {__uint_as_float(u[2 * k][0]), __uint_as_float(u[2 * k][2]), __uint_as_float(u[2 * k + 1][0]),
-                           __uint_as_float(u[2 * k + 1][2])};
-        if (k == 0) {
-          sl = vk;
-        } else {
-          sl.x += vk.x;
-          sl.y += vk.y;
-          sl.z += vk.z;
-          sl.w += vk.w;
-        }
-      }
-      lsum[0] = sl.x;
-      lsum[1] = sl.y;
-      lsum[2] = sl.z;
-      lsum[3] = sl.w;
-#else
       // this lane's SMR rows of every head's partial-logit chunk (MFMA C order [mt][lane][4 rows])
       const __amdgpu_buffer_rsrc_t r = rsrc_of(pb.plx + (int64_t)p * NH * BP * 16 * 2, NH * BP * 16 * 8);
       float uf[NH][SMR];
 #pragma unroll
       for (int k = 0; k < NH; ++k) {
         const int off = k * BP * 16 * 8 + (sm_mt * 64 + lane) * 16 + sm_i0 * 4;
-        if (SMR == 4) {
-          const float4 v = ld_sc1_16(r, off);
-          uf[k][0] = v.x;
-          uf[k][1] = v.y;
-          uf[k][SMR > 2 ? 2 : 0] = v.z;
-          uf[k][SMR > 3 ? 3 : 0] = v.w;
-        } else {
-          const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(r, off, 0, 16);
-          uf[k][0] = __uint_as_float(v[0]);
-          uf[k][1] = __uint_as_float(v[1]);
-        }
+        static_assert(SMR == 2, "one 8-byte load per head");
+        const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(r, off, 0, 16);
+        uf[k][0] = __uint_as_float(v[0]);
+        uf[k][1] = __uint_as_float(v[1]);
       }
       if (hd == 0) P32_STAMP(1, t, 5);
 #pragma unroll
@@ -1388,7 +1142,6 @@ __device__ void head32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, int
         for (int k = 1; k < NH; ++k) sv += uf[k][i];
         lsum[i] = sv;
       }
-#endif
       const float b3 = sB3[c];
 #pragma unroll
       for (int i = 0; i < SMR; ++i) {
@@ -1397,31 +1150,22 @@ __device__ void head32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, int
         const int y = yv[i];
         const float logit = cin ? lsum[i] + b3 : -INFINITY;
         const float mx = row_max16(logit);
-#if P32_FASTSM
         const float ex = cin ? __expf(logit - mx) : 0.f;
         const float se = row_sum16(ex);
         const float logp = logit - (mx + __logf(se));
         cand_v[i] = (cin && logit == mx) ? c : 16;  // argmax reduced behind the dH2 publish
         if (rvalid && c == y) loss_acc -= logp;
-        const float pc = ex * __builtin_amdgcn_rcpf(se);
-#else
-        const float se = row_sum16(cin ? expf(logit - mx) : 0.f);
-        const float logp = logit - (mx + logf(se));
-        const int cand = row_min16((cin && logit == mx) ? c : 16);
-        if (rvalid && c == y) loss_acc -= logp;
-        if (rvalid && c == 0) correct_acc += (cand == y) ? 1.f : 0.f;
         // dlogits: p_c / rows, and for the true class −Σ_{c≠y} p_c / rows rather than (p_y − 1) / rows,
         // which cancels catastrophically on confident rows (p_y → 1). This is the value the
         // reference's fp32 autograd produces through its log_softmax + cross_entropy pair
         // (lightning_model.py:178, :189): scripts/probes/f32_softmax_cancel.py.
-        const float pc = cin ? expf(logp) : 0.f;
-#endif
+        const float pc = ex * __builtin_amdgcn_rcpf(se);
         const float others = row_sum16(c != y ? pc : 0.f);
         sDlog[b * LD16 + c] = (rvalid && cin) ? (c == y ? -others : pc) / (float)rows : 0.f;
       }
     }
     lds_barrier();
-    if (sOk[1] == 0) return;  // a softmax wave gave up on the partial logits
+    if (sOk[1] == 0) return;  // (never taken: see sOk[1] above)
     if (hd == 0) P32_STAMP(1, t, 6);
     // ---- dH2 slice = dlogits · W3[:, slice] ⊙ [H2 > 0]  (K = classes, natural order)
     if (wave < MT) {
@@ -1434,18 +1178,11 @@ __device__ void head32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, int
         const int b = 16 * wave + 4 * h + i;
         const float v = sH2[b * LD16 + c] > 0.f ? acc[i] : 0.f;
         sDH2[b * LD16 + c] = v;
-        if constexpr (LLD)
-          persist::ll_st1p(pb.plain_x, dst + 2 * (b * PD2 + 16 * hd + c), v, tag);  // (XR: written through to every XCD)
-        else
-          persist::pub32(pb.plain_x, dst + b * PD2 + 16 * hd + c, v);
+        persist::pub32(pb.plain_x, dst + b * PD2 + 16 * hd + c, v);  // (XR: written through to every XCD)
       }
     }
-    if constexpr (LLD)
-      lds_barrier();  // sDH2 for the off-path updates (the LL stores need no drain or flag)
-    else
-      persist::publish_p(pb.flags, FPP, p, F_DH2 + hd, pb.fbase + (unsigned)(t + 1), pb.plain_x);
+    persist::publish_p(pb.flags, FPP, p, F_DH2 + hd, target, pb.plain_x);
     if (hd == 0) P32_STAMP(1, t, 7);
-#if P32_FASTSM
     if (wave < SMW) {  // the deferred argmax (accuracy metric)
 #pragma unroll
       for (int i = 0; i < SMR; ++i) {
@@ -1454,7 +1191,6 @@ __device__ void head32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, int
         if (b < rows && c == 0) correct_acc += (cand == yv[i]) ? 1.f : 0.f;
       }
     }
-#endif
 
     // ---- off the critical path: W2 rows (every wave: its two o1 groups), W3 slice (wave 0),
     //      b2 (wave 1), b3 (wave 2, the same arithmetic in every head)
@@ -1566,7 +1302,7 @@ __host__ __device__ inline HeadRLds32 headr_lds32() {
 //   then, beside the owners' backward: partial dW3 / db2 / db3 over the 16 rows -> every head, summed
 //   over the heads in a fixed order, and the W3 / b2 / b3 replicas updated identically in all heads.
 template <int BP, bool ADAM, bool EXTRA, int KS>
-__device__ void headr32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, int r, char* smem, unsigned gen) {
+__device__ void headr32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, int r, char* smem) {
   constexpr int NHR = nhr_of(BP);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1930,7 +1666,10 @@ __global__ __launch_bounds__(NT) void mlp_persistent_f32_epoch(MLPArgs a, MLPPer
     pb.err = err_first;
     pb.fbase = 0;
   }
-  const unsigned gen = __hip_atomic_load(pb.gen + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  // the epoch generation tagged the LL pairs; nothing uses the value now. The relaxed atomic load is
+  // live device code all the same (the compiler keeps it, and every instantiation's schedule moves
+  // without it): it goes with pb.gen and the increment below in a change of its own
+  (void)__hip_atomic_load(pb.gen + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (role == 0 && !attempt) P32_ESTAMP(0);
   // hand-off payloads stay in the XCD's L2 when the whole gang runs on one XCD (KS = 1: blocks
   // b = p mod 8 under round-robin dispatch): +4-7 % rounds/s (profiles/r5_plain). 100 us bound.
@@ -1956,17 +1695,17 @@ __global__ __launch_bounds__(NT) void mlp_persistent_f32_epoch(MLPArgs a, MLPPer
     if (role == 0 && threadIdx.x == 0 && p < 64) g_plain_seen[p] = pb.plain;
   }
   if (role < ng_of(KS))
-    owner32<BP, ADAM, EXTRA, KS, RH, FUSE>(a, pb, p, role, smem_p32, gen);
+    owner32<BP, ADAM, EXTRA, KS, RH, FUSE>(a, pb, p, role, smem_p32);
   else if (RH)
-    headr32<BP, ADAM, EXTRA, KS>(a, pb, p, role - ng_of(KS), smem_p32, gen);
+    headr32<BP, ADAM, EXTRA, KS>(a, pb, p, role - ng_of(KS), smem_p32);
   else
-    head32<BP, ADAM, EXTRA, KS>(a, pb, p, role - ng_of(KS), smem_p32, gen);
+    head32<BP, ADAM, EXTRA, KS>(a, pb, p, role - ng_of(KS), smem_p32);
   if (role == 0) {
     __syncthreads();
     if (!attempt) P32_ESTAMP(3);
     if (threadIdx.x == 0 && __hip_atomic_load(pb.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) {
-      // owner 0 finished every step: the next launch tags its LL pairs with the next generation (a
-      // gang that gave up keeps it; its retry differs by the attempt bit)
+      // owner 0 finished every step: the epoch generation advances (a gang that gave up keeps it). It
+      // tagged the LL pairs; no hand-off reads it now
       // (re-read, not kept live in a VGPR across the epoch)
       __hip_atomic_store(pb.gen + p, __hip_atomic_load(pb.gen + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u, __ATOMIC_RELAXED,
                          __HIP_MEMORY_SCOPE_AGENT);
@@ -2128,12 +1867,10 @@ __global__ __launch_bounds__(NT) void mlp_eval_f32(MLPArgs a) {
 // K split of a launch: MYFYP_F32_KS=1|2 (tests), else the engine's choice, else 1. The occupancy
 // check below may still veto 2.
 // Gang layout: MYFYP_F32_VARIANT=1|2 (A/B runs), else the engine's choice (a.f32_variant), else
-// F32_DEFAULT_VARIANT, except for the Adam + FedProx/SCAFFOLD epoch at K split 1: layout 1's
+// DEFAULT_VARIANT, except for the Adam + FedProx/SCAFFOLD epoch at K split 1: layout 1's
 // instantiation spills VGPRs there (W1's register-resident Adam state plus the per-weight extra
 // term, with LDS full), layout 2's does not, so that one defaults to layout 2.
-#ifndef F32_DEFAULT_VARIANT
-#define F32_DEFAULT_VARIANT 1
-#endif
+constexpr int DEFAULT_VARIANT = 1;
 int f32_ks_v1(const MLPArgs& a);
 
 bool v3_supported(const MLPArgs& a);
@@ -2148,7 +1885,7 @@ int f32_variant(const MLPArgs& a) {
   if (!v && (a.f32_variant >= 1 && a.f32_variant <= 3)) v = a.f32_variant;
   if (!v) {
     const bool adam_extra = a.opt.kind == 0 && (a.anchor != nullptr || a.cg != nullptr);
-    v = (adam_extra && f32_ks_v1(a) == 1) ? 2 : F32_DEFAULT_VARIANT;
+    v = (adam_extra && f32_ks_v1(a) == 1) ? 2 : DEFAULT_VARIANT;
   }
   if (v == 3 && !v3_supported(a)) v = 1;
   if (v == 2 && !mlp_f32v2_supported(a)) v = 1;
@@ -2186,7 +1923,7 @@ const void* f32_fn() {
   return (const void*)mlp_persistent_f32_epoch<BP, ADAM, EXTRA, KS, RH, FUSE>;
 }
 // the fused forward (owner32's FUSE) is instantiated for layout 1 at K split 1 without an extra term
-__host__ __device__ constexpr bool fuse_inst(int KS, bool RH) { return KS == 1 && !RH && !P32_LL_H1 && !P32_BALANCE; }
+__host__ __device__ constexpr bool fuse_inst(int KS, bool RH) { return KS == 1 && !RH; }
 template <int BP, int KS, bool RH = false>
 hipError_t prepare_f32_bp(int lds) {
   const void* fns[4] = {f32_fn<BP, true, false, KS, RH>(), f32_fn<BP, true, true, KS, RH>(), f32_fn<BP, false, false, KS, RH>(),
@@ -2282,10 +2019,11 @@ bool mlp_persistent_f32_supported(const MLPArgs& a) {
   return persistent_f32_lds_ks(a, 1) <= 160 * 1024;
 }
 
-size_t mlp_persistent_f32_h1x_floats(int P, int Bpad) { return (size_t)P * KSLAB * 2 * Bpad * PD1 * H1W; }
+size_t mlp_persistent_f32_h1x_floats(int P, int Bpad) { return (size_t)P * KSLAB * 2 * Bpad * PD1; }
 size_t mlp_persistent_f32_bytes(int P, int Bpad) {
-  // layout 1: H1 partials (fp32) + partial logits and dH2 as LL (value, tag) pairs; layout 2 carves
-  // its own regions from the same allocation
+  // layout 1: H1 partials (fp32) + partial logits and dH2, both at twice their fp32 size (the kernel's
+  // strides were sized for LL (value, tag) pairs); layout 2 carves its own regions from the same
+  // allocation
   const size_t v1 = (mlp_persistent_f32_h1x_floats(P, Bpad) + (size_t)P * ((size_t)NH * Bpad * 16 + (size_t)2 * Bpad * PD2) * 2 + v3_extra_floats(P)) * sizeof(float);
   const size_t v2 = mlp_f32v2_bytes(P, Bpad);
   return v1 > v2 ? v1 : v2;
@@ -2294,8 +2032,6 @@ size_t mlp_persistent_f32_flag_bytes(int P) { return (size_t)P * FPP * persist::
 int mlp_persistent_f32_gang() { return roles_of(1); }
 int mlp_persistent_f32_ks(const MLPArgs& a) { return f32_ks(a); }
 int mlp_persistent_f32_variant(const MLPArgs& a) { return f32_variant(a); }
-int mlp_persistent_f32_x_direct(const MLPArgs& a) { return P32_XDIRECT && f32_variant(a) == 1 ? 1 : 0; }
-int mlp_persistent_f32_x_direct_build() { return P32_XDIRECT; }
 
 // Workgroups one epoch launch needs (its peers' gangs) and how many the device holds at once.
 int mlp_persistent_f32_launch_wgs(const MLPArgs& a) {

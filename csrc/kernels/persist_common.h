@@ -45,16 +45,7 @@ __device__ __forceinline__ unsigned* flag_at(unsigned* flags, int flags_per_peer
 __device__ __forceinline__ void st_wt(void* ptr, unsigned long long v) {  // 8-byte write-through store
   __hip_atomic_store((gu64*)ptr, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-__device__ __forceinline__ void st_wt32(float* ptr, float v) {  // 4-byte write-through store
-  __hip_atomic_store((gu32*)ptr, __builtin_bit_cast(unsigned, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-// 16-byte write-through (sc1) store at byte offset `off` (per lane) of a UNIFORM base: the buffer
-// resource must be wave-uniform (a per-lane base would be read from the first lane only)
-__device__ __forceinline__ void st_wt128(float* base, int bytes, int off, u32x4_t v) {
-  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(base, (short)0, bytes, 0x00020000);
-  __builtin_amdgcn_raw_buffer_store_b128(v, r, off, 0, 16);
-}
 // Hand-off payload stores by gang placement: write-through (sc1) in general; plain when every
 // workgroup of the gang was seen on ONE XCD (the line then stays in that XCD's L2, which is where
 // the consumers' L1-bypassing loads look; sc1 stores drop it, and a same-XCD reader then reads at
@@ -66,6 +57,8 @@ __device__ __forceinline__ void pub32(int plain, float* ptr, float v) {
   else
     __hip_atomic_store((gu32*)ptr, __builtin_bit_cast(unsigned, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+// 16-byte store at byte offset `off` (per lane) of a UNIFORM base: the buffer resource must be
+// wave-uniform (a per-lane base would be read from the first lane only)
 __device__ __forceinline__ void pub128(int plain, float* base, int bytes, int off, u32x4_t v) {
   const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(base, (short)0, bytes, 0x00020000);
   if (plain)
@@ -170,35 +163,11 @@ __device__ __forceinline__ void publish_p(unsigned* flags, int fpp, int p, int i
 // until all reach `target`, then the workgroup meets; every later load of the handed-off bytes is
 // an sc1 load. Bounded: gives up after `ticks` or when another workgroup gave up.
 //
-// PERSIST_WAVE_POLL (A/B build): every wave polls the flags itself and goes on to its payload loads
-// when it sees them, without the workgroup meet (flags are monotone within a launch: a wave that
-// saw them set cannot disagree with another; a wave that times out or sees the error word returns
-// false and the caller's wave leaves the kernel, which a later barrier of the others tolerates).
-// Measured within noise of the meet (profiles/r6z_wavepoll: 641.7 / 616.9 / 637.3 vs 641.1 / 610.3 /
-// 639.8 rounds/s): off.
+// Every wave polling the flags itself, without the workgroup meet, measured within noise of the meet
+// (profiles/r6z_wavepoll: 641.7 / 616.9 / 637.3 vs 641.1 / 610.3 / 639.8 rounds/s) and was not kept;
+// its code last existed in commit f8de7cf.
 __device__ __forceinline__ bool wg_wait(unsigned* flags, int fpp, int p, int idx0, int n, unsigned target, int* err, int* sOk,
                                         unsigned long long ticks = SPIN_TICKS) {
-#ifdef PERSIST_WAVE_POLL
-  {
-    const int lane = threadIdx.x & 63;
-    const unsigned* f = flag_at(flags, fpp, p, idx0 + (lane < n ? lane : 0));
-    const unsigned long long t0 = wall_clock64();
-    for (unsigned it = 1;; ++it) {
-      const unsigned v = lane < n ? __hip_atomic_load((gu32*)f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : target;
-      if (__all(v >= target)) break;
-      if (poll_check(it)) {
-        if (__hip_atomic_load((gu32*)err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) return false;
-        if (wall_clock64() - t0 > ticks) {
-          if (lane == 0) __hip_atomic_store((gu32*)err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          return false;
-        }
-      }
-      poll_sleep();
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    return true;
-  }
-#endif
   if (threadIdx.x < 64) {
     const int lane = threadIdx.x;
     const unsigned* f = flag_at(flags, fpp, p, idx0 + (lane < n ? lane : 0));
@@ -228,114 +197,13 @@ __device__ __forceinline__ bool wg_wait(unsigned* flags, int fpp, int p, int idx
   return ok != 0;
 }
 
-// ---- LL hand-off (the "low latency" protocol of RCCL): every 4-byte payload word travels with a
-// 4-byte tag in ONE naturally aligned 8-byte store, so the consumer's load of the data is its own
-// readiness check — no drain of the producer's stores, no workgroup meet and no flag store on the
-// producer side (the flag protocol above costs two L2 round trips more per hand-off). The tag is
-// unique per (epoch generation, attempt, step): stale pairs of an earlier step or launch never match.
-__device__ __forceinline__ unsigned ll_tag(unsigned gen, unsigned fbase, int t) {
-  return ((gen & 0xFFFu) << 20) | (fbase ? (1u << 19) : 0u) | (unsigned)(t + 1);
-}
-typedef unsigned ll_u32x4 __attribute__((ext_vector_type(4)));
-// 16-byte write-through store of two LL pairs {v0, tag, v1, tag} at byte offset `off` of a uniform base
-__device__ __forceinline__ void ll_st2(float* base, int bytes, int off, float v0, float v1, unsigned tag) {
-  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(base, (short)0, bytes, 0x00020000);
-  const ll_u32x4 v = {__builtin_bit_cast(unsigned, v0), tag, __builtin_bit_cast(unsigned, v1), tag};
-  __builtin_amdgcn_raw_buffer_store_b128(v, r, off, 0, 16);
-}
-// 8-byte write-through store of one LL pair
-__device__ __forceinline__ void ll_st1(float* pair, float v, unsigned tag) {
-  st_wt(pair, ((unsigned long long)tag << 32) | __builtin_bit_cast(unsigned, v));
-}
-// LL stores for a gang found on one XCD (plain: the pair stays in that XCD's L2; one 8- or 16-byte
-// store instruction each, as for the write-through form)
-__device__ __forceinline__ void ll_st1p(int plain, float* pair, float v, unsigned tag) {
-  const unsigned long long w = ((unsigned long long)tag << 32) | __builtin_bit_cast(unsigned, v);
-  if (plain)
-    __hip_atomic_store((gu64*)pair, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  else
-    st_wt(pair, w);
-}
-__device__ __forceinline__ void ll_st2p(int plain, float* base, int bytes, int off, float v0, float v1, unsigned tag) {
-  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(base, (short)0, bytes, 0x00020000);
-  const ll_u32x4 v = {__builtin_bit_cast(unsigned, v0), tag, __builtin_bit_cast(unsigned, v1), tag};
-  if (plain)
-    __builtin_amdgcn_raw_buffer_store_b128(v, r, off, 0, 0);
-  else
-    __builtin_amdgcn_raw_buffer_store_b128(v, r, off, 0, 16);
-}
-// 16-byte L1-bypassing load of two LL pairs
-__device__ __forceinline__ ll_u32x4 ll_ld2(__amdgpu_buffer_rsrc_t r, int off) { return __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 16); }
-__device__ __forceinline__ bool ll_ok2(const ll_u32x4& v, unsigned tag) { return v[1] == tag && v[3] == tag; }
-// Payload words of a received chunk: read them with __uint_as_float(v[i]). amdclang 22 (ROCm 7.2)
-// miscompiles __builtin_bit_cast(float, v[i]) on an ext-vector ELEMENT lvalue: it reads element 0
-// whatever i is (tests/test_kernel_lint.py rejects the pattern).
-
-// Consumer side of an LL hand-off with N 16-byte chunks per lane: `load(k)` issues chunk k's load;
-// spins (s_sleep between polls, chunks that already matched are not reloaded) until every chunk of
-// every lane of the wave carries `tag`. Bounded like wg_wait: false when the gang gave up (err set by
-// any workgroup) or after `ticks`.
-template <int N, class Load>
-__device__ __forceinline__ bool ll_wait(ll_u32x4 (&v)[N], Load load, unsigned tag, int* err, unsigned long long ticks = SPIN_TICKS) {
-#pragma unroll
-  for (int k = 0; k < N; ++k) v[k] = load(k);
-  unsigned long long t0 = 0;
-  for (unsigned it = 1;; ++it) {
-    bool ready = true;
-#pragma unroll
-    for (int k = 0; k < N; ++k) ready = ready && ll_ok2(v[k], tag);
-    if (__all(ready)) return true;
-    if (it == 1 || poll_check(it)) {
-      if (__hip_atomic_load((gu32*)err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) return false;
-      const unsigned long long now = wall_clock64();
-      if (t0 == 0) {
-        t0 = now;
-      } else if (now - t0 > ticks) {
-        if ((threadIdx.x & 63) == 0) __hip_atomic_store((gu32*)err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return false;
-      }
-    }
-    poll_sleep();
-#pragma unroll
-    for (int k = 0; k < N; ++k)
-      if (!ll_ok2(v[k], tag)) v[k] = load(k);
-  }
-}
-
-// Representative wait of an LL hand-off with n <= 64 producers (long waits: the consumer workgroup
-// must not hammer L2 with bulk polls): wave 0, lane k < n, polls one 16-byte chunk of producer k
-// (`probe(k)` issues its load) until its tags match, then the workgroup meets; the bulk loads that
-// follow still verify every tag (ll_wait), since a producer's other chunks may land later.
-template <class Probe>
-__device__ __forceinline__ bool ll_wg_wait(Probe probe, int n, unsigned tag, int* err, int* sOk, unsigned long long ticks = SPIN_TICKS) {
-  if (threadIdx.x < 64) {
-    const int lane = threadIdx.x;
-    const int k = lane < n ? lane : 0;
-    const unsigned long long t0 = wall_clock64();
-    int ok = 1;
-    for (unsigned it = 1;; ++it) {
-      const bool ready = lane >= n || ll_ok2(probe(k), tag);
-      if (__all(ready)) break;
-      if (poll_check(it)) {
-        if (__hip_atomic_load((gu32*)err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) {
-          ok = 0;
-          break;
-        }
-        if (wall_clock64() - t0 > ticks) {
-          if (lane == 0) __hip_atomic_store((gu32*)err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          ok = 0;
-          break;
-        }
-      }
-      poll_sleep();
-    }
-    if (lane == 0) *sOk = ok;
-  }
-  __syncthreads();
-  const int ok = *sOk;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  return ok != 0;
-}
+// An LL hand-off (RCCL's "low latency" protocol: every 4-byte payload word travels with a 4-byte tag
+// in one 8-byte store, so the consumer's load is its own readiness check) was measured against the
+// flag protocol above and lost (profiles/r3e_ll_ab, profiles/r5_ll); its helpers last existed in
+// commit f8de7cf. What it taught stays: read the words of a received vector with
+// __uint_as_float(v[i]) — amdclang 22 (ROCm 7.2) miscompiles __builtin_bit_cast(float, v[i]) on an
+// ext-vector ELEMENT lvalue, it reads element 0 whatever i is (tests/test_kernel_lint.py rejects the
+// pattern).
 
 // Per-step optimizer constants: lr_t = lr / (1 - β1^k), inv = 1 / sqrt(1 - β2^k), k = t0 + t + 1.
 __device__ __forceinline__ void bias_corr(const OptParams& o, int t0, int t, float& lr_t, float& inv) {

@@ -62,12 +62,12 @@ def build(verbose: bool = False, jobs: int = 8, variant: str = "") -> str:
     hipcc = _hipcc()
     obj_dir, lib, extra = OBJ_DIR, LIB, ()
     if variant:
-        # "stamps" or "stamps+NAME=VAL+NAME2" (extra -D macros for timing-only experiment builds)
+        # "stamps"; further "+"-separated parts go to the compiler as -D macros
         parts = variant.split("+")
         tag = variant.replace("+", "_").replace("=", "").replace("mllvm:", "").replace("-", "")
         obj_dir = os.path.join(ROOT, "build", f"obj_{tag}")
         lib = os.path.join(ROOT, "build", tag, "libmyfyp_hip.so")
-        # a part starting with "mllvm:" is a raw backend option (experiment builds: "-mllvm <opt>")
+        # a part starting with "mllvm:" is a raw backend option ("-mllvm <opt>")
         extra = tuple(["-DMLP_STAMPS"] if parts[0] == "stamps" else [])
         for m in parts[1:]:
             extra += ("-mllvm", m[len("mllvm:"):]) if m.startswith("mllvm:") else (f"-D{m}",)
