@@ -69,7 +69,8 @@ hipError_t mlp_f32v2_prepare(const MLPArgs& a);
 void mlp_f32v2_launch(const MLPArgs& a, const MLPPersistF32Bufs& pb, hipStream_t s);
 
 // Optional phase timestamps (build with -DMLP_STAMPS): peer 0's owner 0 (role 0) and head 0 (role 1),
-// steps < 32, read with mlp_debug_persistent_f32_stamps (wall_clock64 ticks, 100 MHz).
+// steps < 128, read with mlp_debug_persistent_f32_stamps (wall_clock64 ticks, 100 MHz). Owner slot 8
+// is wave 1's end of C2 (fused loop), every other stamp is thread 0's.
 // Epoch-level stamps of peer 0's owner 0: [0] kernel entry, [1] first step start, [2] gang commit
 // passed, [3] write-back done (mlp_debug_persistent_f32_epoch_stamps).
 #ifdef MLP_STAMPS
@@ -83,6 +84,11 @@ __device__ unsigned long long g_p32_epoch[4];
   do {                                                       \
     if (p == 0 && threadIdx.x == 0) g_p32_epoch[i] = wall_clock64(); \
   } while (0)
+// owner slot 8: the end of C2 as lane 0 of wave 1 sees it (three K steps; thread 0's wave 0 has four)
+#define P32_STAMP_W1(t, i)                                                                   \
+  do {                                                                                       \
+    if (p == 0 && threadIdx.x == 64 && (t) < 128) g_p32_stamps[0][t][i] = wall_clock64(); \
+  } while (0)
 extern "C" int mlp_debug_persistent_f32_stamps(void* out) {
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_p32_stamps), sizeof(g_p32_stamps)) == hipSuccess ? 0 : 1;
 }
@@ -95,6 +101,9 @@ extern "C" int mlp_debug_persistent_f32_epoch_stamps(void* out) {
   } while (0)
 #define P32_ESTAMP(i) \
   do {                \
+  } while (0)
+#define P32_STAMP_W1(t, i) \
+  do {                     \
   } while (0)
 #endif
 
@@ -128,6 +137,11 @@ using namespace f32k;
 //   * heads' softmax on library expf / logf, p = exp(logp), argmax inline: softmax 1.16 vs 0.92 us,
 //     615.8 / 614.0 / 615.6 vs 626.4 / 627.4 / 628.0 rounds/s (profiles/r6t_fastsm). The chain kept:
 //     v_exp / v_log (__expf / __logf, within 2 ulp), p = e / Σe, the argmax behind the dH2 publish.
+//   * C2's straight body chosen inside the step loop (one scalar branch per step): 17-25 VGPRs spilled
+//     in the bench instantiation; and a scheduling fence between the straight body's K steps: 682.8 /
+//     683.8 / 682.7 vs 688.4 / 688.4 / 689.9 rounds/s unfenced (profiles/r9_c2_straight). Kept: one
+//     step loop per body, unfenced, 700.8-703.2 vs the parent's 673.9-686.2 (docs/PERFORMANCE.md "A
+//     straight-line C2").
 //
 // heads' log-softmax over 2 x MT waves, two rows per lane (MT waves with four rows each: 519.9 / 522.5
 // vs 529.8 / 530.6 rounds/s, profiles/r4g_softmax8): the per-row DPP reductions and exp / log chains
@@ -437,8 +451,12 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
       }
     }
   };
-  {  // columns past D0 (the bias column's K step) are zero for the whole epoch
-    const int z0 = D0 - C0, z1 = KS1 * 32;
+  {  // columns past D0 (the bias column's K step) are zero for the whole epoch. The chunk at column D0
+     // itself is left out: xw_stage below and every C2 write it whole (bias input, then zeros), and no
+     // barrier stands between this fill and xw_stage. Filled here too, another wave's zeros could
+     // land on the bias inputs of step 0 wherever the bias chunk's wave had no loads to wait for
+     // before it (D0 < 256: wrong and irreproducible first steps)
+    const int z0 = D0 - C0 + 8, z1 = KS1 * 32;
     if (z0 < z1)
       for (int e = tid; e < BP * (z1 - z0); e += NT) {
         const int r = e / (z1 - z0), q = e % (z1 - z0);
@@ -468,10 +486,11 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
   };
   // forward contribution of this wave's K step q (slot q) to the H1 slice, with the weights as they
   // are now and the batch tile currently staged in LDS. The LDS-resident K step (q == RQ, KS = 1:
-  // K step 24, D0 > 767) is wave 0's.
-  auto fwd_kstep = [&](int q, f32x4(&acc)[MT]) {
+  // K step 24, D0 > 767) is wave 0's. chk = false (C2's straight body): the caller knows the K step
+  // exists, no test.
+  auto fwd_kstep = [&](int q, f32x4(&acc)[MT], bool chk = true) __attribute__((always_inline)) {
     const int s = wave + 8 * q;
-    if (s >= KS1) return;
+    if (chk && s >= KS1) return;
     // lane coordinates laundered per K step: the compiler would otherwise hoist every LDS address
     // of the loop out of it and spill them
     int lq = lane;
@@ -591,6 +610,20 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
   persist::BiasCorr bc;
   bc.init(o, ctl.z);
   float lr_t = 0.f, inv_bc2 = 0.f;
+  // C2's straight-line body (layout 1, K split 1): taken by a wave whose register-resident K steps
+  // wave + 8q, q < RQ, all exist (D0 >= 736: every wave), with the launch's switch on. Wave-uniform.
+  constexpr bool SI = KS == 1 && !RH && !EXTRA;
+  const bool straight = SI && pb.c2_straight != 0 && wave + 8 * (RQ - 1) < KS1;
+  // One step loop per C2 body, chosen once per epoch (the `body` loop is unrolled, ST a constant in
+  // each copy): with both bodies inside one step loop the bench instantiation spilled 17-25 VGPRs,
+  // each loop on its own fits. Waves of one workgroup may run different loops (D0 < 736): they meet at
+  // the same barriers in the same order. The `body` loop stays where there is no straight body (one
+  // trip): with it the loop-carried Adam state is no longer copied around the step loop's back-edge
+  // (-30 to -70 VGPRs in every Adam instantiation, profiles/r9_c2_straight/isa.md).
+#pragma unroll
+  for (int body = 0; body < (SI ? 2 : 1); ++body) {
+  const bool ST = SI && body == 1;
+  if (SI && straight != ST) continue;
   for (int t = 0; t < nsteps; ++t) {
     int tv = tid;  // per-iteration opaque thread index (addresses re-derived each step: VGPR pressure)
     asm volatile("" : "+v"(tv));
@@ -643,16 +676,30 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
     uint4 xqf[XQF];
     const __amdgpu_buffer_rsrc_t r_xn =
         rsrc_of(a.Xb16 + ((int64_t)p * a.xb_rows + (int64_t)(t + 1) * a.B) * D0, more ? rows_at(a, n, t + 1) * D0 * 2 : 0);
-    auto xq_load = [&](int q) {
+    // chk = false (C2's straight body): no test for the K step; one past the owner's last has every
+    // column >= 32 KS1 > D0, so all its offsets are out of range and it loads zeros.
+    auto xq_load = [&](int q, bool chk = true) __attribute__((always_inline)) {
       const int s = wave + 8 * q;
-      if (s >= KS1) return;  // wave-uniform
+      if (chk && s >= KS1) return;  // wave-uniform
+      // the straight body's calls take the step's laundered lane: their offsets differ by constants
+      // from K step to K step, where a lane laundered per call costs a 32-bit multiply per chunk
       int lx = lane;
-      asm volatile("" : "+v"(lx));
+      if (chk)
+        asm volatile("" : "+v"(lx));
+      else
+        lx = tv & 63;
 #pragma unroll
       for (int kk = 0; kk < XQF; ++kk) {
         const int idx = kk * 64 + lx;
         const int r = idx >> 2, gcol = C0 + 32 * s + 8 * (idx & 3);
-        const unsigned off = gcol < D0 ? (unsigned)(r * D0 + gcol) * 2u : 0x7FFFFFF0u;
+        // the offset is laundered on both sides of the select (not volatile: no ordering against the
+        // memory operations around): fed by the address arithmetic and feeding the load directly, the
+        // select was lowered to exec-mask branches around a duplicated load, and with the load alone
+        // fenced off, to an exec-masked address computation, instead of a v_cndmask on the offset
+        unsigned off = (unsigned)(r * D0 + gcol) * 2u;
+        asm("" : "+v"(off));
+        off = gcol < D0 ? off : 0x7FFFFFF0u;
+        asm("" : "+v"(off));
         xqf[kk] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r_xn, off, 0, 0));
       }
     };
@@ -771,12 +818,25 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
       for (int mt = 0; mt < (FUSE ? MT : 1); ++mt) accF[mt] = zero4();
       const int rows_next = more ? rows_at(a, n, t + 1) : 0;
       const bf16* xnext = a.Xb16 + ((int64_t)p * a.xb_rows + (int64_t)(t + 1) * a.B) * D0;
+      // The K-step loop, in two bodies, one per step loop (`straight`, `body`, above). ST = false, the
+      // guarded body: every K step behind s < KS1, its stores and fused forward behind `more`, the
+      // stores per lane behind the column tests. ST = true, the straight body: K steps q < RQ are
+      // known to exist and run with no test at all, so they share one basic block and carry no
+      // "K step skipped" copies of the Adam state; every lane stores every chunk (the loaded value is
+      // already zero at and past column D0, the bias chunk ORs its 1.0 in; rewriting the zero columns
+      // is idempotent, and chunk columns stay below 32 KS1 < LDX); `more` guards nothing here: on the
+      // last step r_xn has 0 bytes and rows_next is 0, so zeros are staged, and the forward runs
+      // into accF, which is published only under `more`. Nothing reads sX or accF after the last
+      // step: gang_commit touches sOk only, the write-back reads the weight registers and sW1x, and
+      // the debug replica update reads sH1 and the dH2 exchange buffer. The LDS-resident K step
+      // (q == RQ) keeps its wave-uniform test in both bodies and has the branch-free stores in both.
 #pragma unroll
       for (int q = 0; q < (KS == 1 ? RQ + 1 : RQ); ++q) {
+        const bool STq = ST && q < RQ;  // the LDS-resident K step runs in its guarded form in either body
         // wave w owns K step w + 8q, both 16-column halves (tt = 0, 1); q == RQ (KS = 1): the
         // LDS-resident K step, wave 0's
         const int s = wave + 8 * q;
-        if (s < KS1) {
+        if (STq || s < KS1) {
           int lq = lane;
           asm volatile("" : "+v"(lq));
           const bf16* dfrag = sD3 + (lq & 15) * LDT + 8 * (lq >> 4);
@@ -792,6 +852,14 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
             }
             const int idx = kk * 64 + lv;
             const int r = idx >> 2, col = 32 * s + 8 * (idx & 3), gcol = C0 + col;
+            if (STq) {  // as xq_load: rows past the batch and columns past D0 load as zero
+              unsigned off = (unsigned)(r * D0 + gcol) * 2u;
+              asm("" : "+v"(off));
+              off = gcol < D0 ? off : 0x7FFFFFF0u;
+              asm("" : "+v"(off));
+              xq[kk] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r_xn, off, 0, 0));
+              continue;
+            }
             const bool xl = more && gcol < D0 && r < rows_next;
             xq[kk] = xl ? *reinterpret_cast<const uint4*>(xnext + (unsigned)(r * D0 + gcol)) : uint4{0u, 0u, 0u, 0u};
           }
@@ -820,27 +888,36 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
               *reinterpret_cast<float4*>(sW1x + 1024 + off) = v;
             }
           }
-          if (more) {
+          if (STq || more) {
 #pragma unroll
             for (int kk = 0; kk < XQ; ++kk) {
               const int idx = kk * 64 + lv;
               const int r = idx >> 2, col = 32 * s + 8 * (idx & 3), gcol = C0 + col;
-              if (gcol < D0)
+              if (STq || (SI && q == RQ)) {  // branch-free: xq is zero at and past column D0 (D0 % 8 == 0)
+                // (one 16-byte vector: the struct with one member rewritten was stored in 8-byte halves)
+                const unsigned b1 = (gcol == D0 && r < rows_next) ? 0x3F80u : 0u;  // bias input: bf16 1.0
+                *reinterpret_cast<u32x4*>(sX + r * LDX + col) = u32x4{xq[kk].x | b1, xq[kk].y, xq[kk].z, xq[kk].w};
+              } else if (gcol < D0) {
                 *reinterpret_cast<uint4*>(sX + r * LDX + col) = xq[kk];
-              else if (gcol == D0)
+              } else if (gcol == D0) {
                 *reinterpret_cast<uint4*>(sX + r * LDX + col) = bias_chunk(r < rows_next);
+              }
             }
           }
         }
         // fused loop: the K step's weights are updated and its columns of X(t + 1) staged, both by
         // this wave (its own registers and LDS writes, which complete in order): no barrier
         if constexpr (FUSE) {
-          if (q + 1 < (KS == 1 ? RQ + 1 : RQ)) xq_load(q + 1);
-          if (more) fwd_kstep(q, accF);
+          if (q + 1 < (KS == 1 ? RQ + 1 : RQ)) xq_load(q + 1, !STq);
+          if (STq)
+            fwd_kstep(q, accF, false);
+          else if (more)
+            fwd_kstep(q, accF);
         }
       }
       if constexpr (FUSE) {
         if (g == 0) P32_STAMP(0, t, 6);
+        if (g == 0) P32_STAMP_W1(t, 8);
         // H1(t + 1): sRed is free (C1's partials were consumed before C1's last barrier), and so is
         // the exchange slab of parity (t + 1) & 1 (the heads read H1(t - 1) before they produced
         // dH2(t)). The reduction's barrier is the one that ends the step.
@@ -855,7 +932,8 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
       __syncthreads();
       if (g == 0) P32_STAMP(0, t, 6);
     }
-  }
+    }  // step loop (kept at its indentation inside the body loop)
+  }    // body loop
 
   if (!gang_commit<KS, RH, BP>(a, pb, p, g, sOk)) return;
   if (g == 0) P32_ESTAMP(2);
@@ -2111,6 +2189,26 @@ static int f32_fwd_fuse_mode() {
 extern "C" int mlp_set_f32_fwd_fuse(int mode) { return g_fuse_override.exchange(mode < 0 ? -1 : mode); }
 extern "C" int mlp_f32_fwd_fuse_last() { return g_fuse_last.load(std::memory_order_relaxed); }
 
+// MYFYP_F32_C2_STRAIGHT: 1 (default) the owners of layout 1 at K split 1 run C2's straight-line body
+// in every wave whose register-resident K steps all exist, 0 the guarded body everywhere (A/B; same
+// bits either way); mlp_set_f32_c2_straight overrides it (tests; -1: back to the environment). The
+// switch reaches the kernel as pb.c2_straight. mlp_f32_c2_straight_last: what the last layout-1 epoch
+// launch could take: 1 if the switch was on and D0 gives every wave its K steps (K split 1, 24 K steps
+// or more: D0 >= 736), else 0 (-1: none yet).
+static std::atomic<int> g_straight_override{-1};
+static std::atomic<int> g_straight_last{-1};
+static int f32_c2_straight_mode() {
+  const int o = g_straight_override.load(std::memory_order_relaxed);
+  if (o >= 0) return o;
+  static const int v = [] {
+    const char* e = getenv("MYFYP_F32_C2_STRAIGHT");
+    return e != nullptr ? atoi(e) : 1;
+  }();
+  return v;
+}
+extern "C" int mlp_set_f32_c2_straight(int mode) { return g_straight_override.exchange(mode < 0 ? -1 : mode); }
+extern "C" int mlp_f32_c2_straight_last() { return g_straight_last.load(std::memory_order_relaxed); }
+
 hipError_t mlp_launch_persistent_f32_epoch(const MLPArgs& a, const MLPPersistF32Bufs& pb_in, hipStream_t s, bool zero_flags, const int* active) {
   MLPPersistF32Bufs pb = pb_in;
   pb.plain_ok = mlp_plain_pub_mode();
@@ -2129,6 +2227,8 @@ hipError_t mlp_launch_persistent_f32_epoch(const MLPArgs& a, const MLPPersistF32
   const size_t lds = persistent_f32_lds_ks(a, KS, rh);
   const bool fuse = f32_fwd_fuse_mode() != 0 && fuse_inst(KS, rh) && a.anchor == nullptr && a.cg == nullptr;
   g_fuse_last.store(fuse ? 1 : 0, std::memory_order_relaxed);
+  pb.c2_straight = f32_c2_straight_mode() != 0 ? 1 : 0;
+  g_straight_last.store(pb.c2_straight && !rh && KS == 1 && 7 + 8 * (rq_of(1) - 1) < ks1_of(a.D0) ? 1 : 0, std::memory_order_relaxed);
   // groups of ppl peers: one launch each (a launch's gangs must all be co-resident), then the
   // recovery launches (attempt 1): a no-op exit for every gang that did not give up
   // (a group with no active peer is not launched: at one peer per device and K split 8 the other

@@ -281,8 +281,9 @@ __device__ void owner_v2(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, i
       }
     }
   };
-  {  // columns past D0 (the bias column's K step) are zero for the whole epoch
-    const int z0 = D0, z1 = KS1 * 32;
+  {  // columns past D0 (the bias column's K step) are zero for the whole epoch; the chunk at column D0
+     // is xw_stage's alone (no barrier between this fill and it: as in mlp_persistent_f32.hip)
+    const int z0 = D0 + 8, z1 = KS1 * 32;
     for (int e = tid; e < BP * (z1 - z0); e += NT) {
       const int r = e / (z1 - z0), q = e % (z1 - z0);
       sX[r * LDX + z0 + q] = (bf16)0.f;

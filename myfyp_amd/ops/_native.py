@@ -108,6 +108,8 @@ _SIGNATURES = {
     "mlp_debug_plain_seen": (c_int, [c_void_p]),
     "mlp_set_f32_fwd_fuse": (c_int, [c_int]),  # owners' fused next-step forward: 1 / 0 (-1: MYFYP_F32_FWD_FUSE)
     "mlp_f32_fwd_fuse_last": (c_int, []),  # path of the last fp32 layout-1/3 epoch launch (1 fused, 0 separate)
+    "mlp_set_f32_c2_straight": (c_int, [c_int]),  # owners' straight-line C2 body: 1 / 0 (-1: MYFYP_F32_C2_STRAIGHT)
+    "mlp_f32_c2_straight_last": (c_int, []),  # 1: the last fp32 layout-1 epoch launch could take it in every wave
     "mlp_debug_stamps": (c_int, [c_void_p]),  # only in the -DMLP_STAMPS diagnostics build
     "mlp_debug_persistent_f32_stamps": (c_int, [c_void_p]),  # likewise
 }

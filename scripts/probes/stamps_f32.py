@@ -68,6 +68,15 @@ for t in range(2, 14):
 m = np.median(np.array(rows), axis=0)
 no = len(do) + 1
 print("median owner", " ".join(f"{x:5.2f}" for x in m[:no]), " head", " ".join(f"{x:5.2f}" for x in m[no:]))
+straight_last = getattr(lib, "mlp_f32_c2_straight_last", None)
+if straight_last is not None:
+    print("C2 body:", "straight (MYFYP_F32_C2_STRAIGHT=1)" if straight_last() == 1 else "guarded")
+if fused:
+    # owner slot 8: the end of C2 as lane 0 of wave 1 sees it. Wave 1 owns three K steps, thread 0's wave 0
+    # four (K step 24): slot 6 minus slot 8 is how long waves 1..7 wait for wave 0 at the step's barrier
+    w1 = np.array([[(st[0, t, 8] - st[0, t, 5]) / 100.0, (st[0, t, 6] - st[0, t, 8]) / 100.0] for t in range(2, 14)])
+    print("C2 + fused fwd of wave 1 (us):", " ".join(f"{x:5.2f}" for x in w1[:, 0]), "| median", f"{np.median(w1[:, 0]):5.2f}")
+    print("wave 0 ends C2 after wave 1 by (us):", " ".join(f"{x:5.2f}" for x in w1[:, 1]), "| median", f"{np.median(w1[:, 1]):5.2f}")
 print("owner H1 published -> head H1 seen (us; fused: negative while the head is still in step t - 1):", [round((st[1, t, 1] - st[0, t, 2]) / 100.0, 2) for t in range(2, 10)])
 print("head dH2 published -> owner dH2 seen (us):", [round((st[0, t, 4] - st[1, t, 7]) / 100.0, 2) for t in range(2, 10)])
 print("head PL published -> head PL all seen (us):", [round((st[1, t, 5] - st[1, t, 4]) / 100.0, 2) for t in range(2, 10)])
