@@ -1,12 +1,13 @@
-"""Krum / TrimmedMean aggregation on the collective plane: device path against the generic path.
+"""Krum / TrimmedMean / GeometricMedian aggregation on the collective plane: device path against the generic path.
 
     python benchmarks/bench_robust_agg.py                      # MLP (n = 235,146) and ResNet-18, 8 peers
     python benchmarks/bench_robust_agg.py --models mlp --repeats 30
+    python benchmarks/bench_robust_agg.py --aggregators geometric_median,krum
 
 For each model and aggregator the same 8 co-located peers are aggregated two ways, alternating in
 one process on identical inputs (the rows are restored, untimed, before every call):
 
-* device : ``weights_plane.aggregate_krum`` / ``aggregate_trimmed_mean`` (the kernels of
+* device : ``weights_plane.aggregate_krum`` / ``aggregate_trimmed_mean`` / ``aggregate_geometric_median`` (the kernels of
   ``csrc/kernels/fl_ops.hip`` on the live rows), host clock around the call plus a device
   synchronise;
 * generic: what ``join_aggregation`` does for an aggregator without a device path — a wire model
@@ -15,7 +16,10 @@ one process on identical inputs (the rows are restored, untimed, before every ca
 
 The two row-reading kernels are then timed alone with device events over a window of back-to-back
 calls, and their achieved GB/s computed from the bytes the algorithm needs (K rows read; the mean
-reads the chosen rows and writes P rows). One JSON line per (model, aggregator). Needs a GPU:
+reads the chosen rows and writes P rows). The geometric median's distance/reweight pair is the
+difference of a 5-step and a 1-step call, divided by 4: allocation and call overhead cancel; the
+whole 1-step call (screen + one step: two pairs) is reported next to Krum's distance/select pair,
+which is timed in the same process for that. One JSON line per (model, aggregator). Needs a GPU:
 ``--device cpu`` only rehearses the plumbing and its timings mean nothing.
 """
 
@@ -38,6 +42,7 @@ FLIPPED = 5
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--models", default="mlp,resnet18")
+    ap.add_argument("--aggregators", default="krum,trimmed_mean,geometric_median")
     ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"])
     ap.add_argument("--repeats", type=int, default=20, help="timed device calls per case (generic: --generic-repeats)")
     ap.add_argument("--generic-repeats", type=int, default=5)
@@ -95,11 +100,12 @@ def run_case(model_name: str, agg_name: str, args) -> dict:
     import torch
 
     from myfyp_amd import ops
-    from myfyp_amd.learning.aggregators import Krum, TrimmedMean
+    from myfyp_amd.learning.aggregators import GeometricMedian, Krum, TrimmedMean
     from myfyp_amd.parallel import weights_plane
     from myfyp_amd.parallel.federation import Federation
 
-    make = (lambda: Krum(num_byzantine=1, multi=3)) if agg_name == "krum" else (lambda: TrimmedMean(beta=0.125))
+    make = {"krum": lambda: Krum(num_byzantine=1, multi=3), "trimmed_mean": lambda: TrimmedMean(beta=0.125),
+            "geometric_median": lambda: GeometricMedian(iters=3)}[agg_name]
     Federation.reset()
     fed = Federation.init()
     nodes = build_nodes(model_name, make)
@@ -114,7 +120,8 @@ def run_case(model_name: str, agg_name: str, args) -> dict:
         base = torch.randn(n, generator=g) * 0.05
         rows0 = torch.stack([(-base if i == FLIPPED else base + 1e-3 * (1 + 0.15 * i) * 0.05 * torch.randn(n, generator=g)) for i in range(PEERS)]).to(dev)
         agg = nodes[0].aggregator
-        device_fn = weights_plane.aggregate_krum if agg_name == "krum" else weights_plane.aggregate_trimmed_mean
+        device_fn = {"krum": weights_plane.aggregate_krum, "trimmed_mean": weights_plane.aggregate_trimmed_mean,
+                     "geometric_median": weights_plane.aggregate_geometric_median}[agg_name]
 
         def restore() -> None:
             with torch.no_grad():
@@ -172,6 +179,23 @@ def run_case(model_name: str, agg_name: str, args) -> dict:
             kernels["pairwise_sqdist+select"] = {"ms": round(ms_sel, 4), "GBps": round(PEERS * n * 4 / ms_sel / 1e6, 1), "bytes": "K rows read"}
             kernels["coef_mean"] = {"ms": round(ms_mean, 4), "GBps": round((3 + PEERS) * n * 4 / ms_mean / 1e6, 1), "bytes": "3 chosen rows read, P rows written",
                                     "note": "difference of the two windows"}
+        elif agg_name == "geometric_median":
+            scratch = [torch.empty(n, dtype=torch.float32, device=dev) for _ in range(PEERS)]
+            ms_1 = event_ms(dev, lambda: ops.geometric_median_into(flats, [], w, 1), it, wu)
+            ms_5 = event_ms(dev, lambda: ops.geometric_median_into(flats, [], w, 5), it, wu)
+            ms_3 = event_ms(dev, lambda: ops.geometric_median_into(flats, [], w, 3), it, wu)
+            ms_all = event_ms(dev, lambda: ops.geometric_median_into(flats, scratch, w, 3), it, wu)
+            ms_krum = event_ms(dev, lambda: ops.krum_into(flats, [], w, 1, 3), it, wu)
+            ms_pair = max((ms_5 - ms_1) / 4, 1e-6)
+            ms_mean = max(ms_all - ms_3, 1e-6)
+            kernels["gm_dist+reweight"] = {"ms": round(ms_pair, 4), "GBps": round(PEERS * n * 4 / ms_pair / 1e6, 1), "bytes": "K rows read",
+                                           "note": "(5-step call - 1-step call) / 4"}
+            kernels["screen+1 step (2 pairs, whole call)"] = {"ms": round(ms_1, 4), "GBps": round(2 * PEERS * n * 4 / ms_1 / 1e6, 1), "bytes": "K rows read twice"}
+            kernels["screen+3 steps (4 pairs, whole call)"] = {"ms": round(ms_3, 4), "GBps": round(4 * PEERS * n * 4 / ms_3 / 1e6, 1), "bytes": "K rows read 4 times"}
+            kernels["krum pairwise_sqdist+select (whole call, same process)"] = {"ms": round(ms_krum, 4), "GBps": round(PEERS * n * 4 / ms_krum / 1e6, 1),
+                                                                               "bytes": "K rows read"}
+            kernels["coef_mean"] = {"ms": round(ms_mean, 4), "GBps": round(2 * PEERS * n * 4 / ms_mean / 1e6, 1), "bytes": "K rows read, P rows written",
+                                    "note": "difference of the two windows"}
         else:
             scratch = [torch.empty(n, dtype=torch.float32, device=dev) for _ in range(PEERS)]
             ms = event_ms(dev, lambda: ops.trimmed_mean_into(flats, scratch, 1), it, wu)
@@ -196,7 +220,7 @@ def main() -> None:
     Settings.DEVICE = args.device
     Settings.LOG_LEVEL = "WARNING"
     for model_name in [m for m in args.models.split(",") if m]:
-        for agg_name in ("krum", "trimmed_mean"):
+        for agg_name in [a for a in args.aggregators.split(",") if a]:
             print(json.dumps(run_case(model_name, agg_name, args)), flush=True)
 
 

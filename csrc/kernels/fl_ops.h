@@ -50,6 +50,15 @@ unsigned fl_krum_grid(int64_t n, int K);
 void fl_krum_select(float* work, const RowPtrs& rows, const RowW& w, int K, int f, int m, int64_t n, double* dist, double* score, float* coef,
                     hipStream_t s);
 void fl_coef_mean(const OutPtrs& outs, int P, const RowPtrs& rows, int K, const float* coef, int64_t n, hipStream_t s);
+// Geometric median (smoothed Weiszfeld, iters steps) of rows 0..K-1: a screen pass that rejects the
+// rows whose sum of squares is not a finite float, then per step the distances to the current
+// point (from differences to a reference row) and coef <- w_k / max(nu, d_k), normalised. Device
+// outputs coef[K] (float), dist[K] (double, the last step's distances) and obj[iters] (double,
+// sum of w_k d_k per step). work holds fl_geomed_work(n, K) floats; the grid is fl_krum_grid(n, K).
+// 2 (iters + 1) launches; fl_coef_mean then writes the outputs.
+inline int64_t fl_geomed_work(int64_t n, int K) { return (int64_t)fl_krum_grid(n, K) * K + 16; }
+void fl_geometric_median(float* work, const RowPtrs& rows, const RowW& w, int K, int iters, double nu, int64_t n, float* coef, double* dist,
+                         double* obj, hipStream_t s);
 // SCAFFOLD server step, packed buffer [Σ w_k dy_k | Σ w_k | Σ dc_k | K] (2n + 2 floats):
 //   reduce: buf <- the local contributions (before the cross-rank all-reduce)
 //   apply : out rows <- x_start + glr · buf[0:n] / buf[n];  c <- (c_init ? 0 : c) + buf[n+1:2n+1] / buf[2n+1]

@@ -548,6 +548,169 @@ __global__ __launch_bounds__(FL_BLOCK) void k_coef_mean(OutPtrs outs, int P, Row
   }
 }
 
+// Geometric median (RFA: Pillutla et al., 2019, smoothed Weiszfeld) in 2(T+1)+1 launches, built
+// like Krum above: per-block slabs, one block that sums them in double, no float atomics, no
+// cross-block synchronisation, nothing for the host to read.
+//   k_gm_dist<K>  : per block the K partial sums Σ (x_k − z)² of its coordinates, z = Σ_j c_j x_j,
+//                   stored into the block's slab of work[grid][K]
+//   k_gm_reweight : one block sums the slabs in a fixed order (double) and, screen: rejects the
+//                   rows whose Σ x² is not finite and writes the start coefficients; iterate:
+//                   writes dist, obj[t] and the next coefficients β_k / Σβ, β_k = ŵ_k / max(ν, d_k)
+//   k_coef_mean<K>: out rows <- Σ_k coef[k] · row_k
+// x_k − z is taken as (x_k − x_r) − Σ_j c_j (x_j − x_r), r the lowest row of coefficient != 0: z
+// itself is never rounded to fp32. Rows differ by ~1e-3 of their norm (see Krum), so rounding z
+// would cost x_k − z its last three digits; the differences from x_r are exact or nearly so.
+// With coef == nullptr every coefficient is 0 and x_r is taken as 0: the sums are |x_k|², which is
+// the screen pass.
+template <int K, bool VEC>
+__global__ __launch_bounds__(FL_BLOCK) void k_gm_dist(float* __restrict__ work, RowPtrs rows, const float* __restrict__ coef, int64_t n) {
+  __shared__ float part[KRUM_WAVES][K];
+  float c[K], acc[K];
+  int r = -1;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    c[k] = coef != nullptr ? coef[k] : 0.f;
+    if (r < 0 && c[k] != 0.f) r = k;
+    acc[k] = 0.f;
+  }
+  const int64_t groups = (n + 3) / 4;
+  const int64_t stride = (int64_t)gridDim.x * FL_BLOCK;
+  for (int64_t g = (int64_t)blockIdx.x * FL_BLOCK + threadIdx.x; g < groups; g += stride) {
+    float4 v[K];
+    // one decision for all K rows, so that the K vector loads are issued back to back (a branch
+    // per row makes each load wait for the one before)
+    if (VEC && 4 * g + 4 <= n) {
+#pragma unroll
+      for (int k = 0; k < K; ++k) v[k] = reinterpret_cast<const float4*>(rows.p[k])[g];
+    } else {
+#pragma unroll
+      for (int k = 0; k < K; ++k) v[k] = load4<false>(rows.p[k], g, n);
+    }
+    // the reference row by a wave-uniform predicated copy: v[] stays in registers
+    float4 xr = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+      if (k == r) xr = v[k];
+    float4 m = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      v[k].x -= xr.x; v[k].y -= xr.y; v[k].z -= xr.z; v[k].w -= xr.w;
+      if (c[k] == 0.f) continue;  // a rejected row may hold NaN
+      m.x = fmaf(c[k], v[k].x, m.x); m.y = fmaf(c[k], v[k].y, m.y); m.z = fmaf(c[k], v[k].z, m.z); m.w = fmaf(c[k], v[k].w, m.w);
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const float dx = v[k].x - m.x, dy = v[k].y - m.y, dz = v[k].z - m.z, dw = v[k].w - m.w;
+      acc[k] += (dx * dx + dy * dy) + (dz * dz + dw * dw);
+    }
+  }
+  // wave reduction (xor butterfly: a fixed order), then the block's waves through LDS in wave order
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    float s = acc[k];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+    acc[k] = s;
+  }
+  const int wave = threadIdx.x / 64;
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) part[wave][k] = acc[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < K) {
+    float s = part[0][threadIdx.x];
+#pragma unroll
+    for (int w = 1; w < KRUM_WAVES; ++w) s += part[w][threadIdx.x];
+    work[(int64_t)blockIdx.x * K + threadIdx.x] = s;  // every block stores its whole slab
+  }
+}
+
+// One block. The slabs work[G][K] are summed in double in k_krum_select's fixed two-level order
+// (C = KRUM_SELECT_BLOCK / K chunks of consecutive slabs, then the chunks in chunk order); thread 0
+// then runs the K-term arithmetic in double, k ascending. what[K] holds ŵ: the sample weights with
+// 0 for a rejected row (all 1 where every valid weight is 0), written by the screen call and read
+// by the iterations. No valid row: ŵ = 0 and coef = w / Σw (or 1/K), which every iteration keeps
+// (Σβ = 0), so the output is the plain mean and shows the NaN; dist is NaN then.
+#define GM_SCREEN 0
+#define GM_ITERATE 1
+__global__ __launch_bounds__(KRUM_SELECT_BLOCK) void k_gm_reweight(const float* __restrict__ work, int G, int K, int mode, int t, RowW w, double nu,
+                                                                   float* __restrict__ what, float* __restrict__ coef, double* __restrict__ dist,
+                                                                   double* __restrict__ obj) {
+  __shared__ double part[KRUM_SELECT_BLOCK];
+  __shared__ double sum[16], d[16], beta[16];
+  const int tid = threadIdx.x;
+  const int C = KRUM_SELECT_BLOCK / K;  // K <= 16: at least 64 chunks
+  if (tid < C * K) {
+    const int p = tid % K, c = tid / K;
+    const int per = (G + C - 1) / C;
+    const int g1 = min(G, (c + 1) * per);
+    int g = c * per;
+    double s = 0.0;
+    for (; g + 8 <= g1; g += 8) {
+      float v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) v[u] = work[(int64_t)(g + u) * K + p];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) s += (double)v[u];
+    }
+    for (; g < g1; ++g) s += (double)work[(int64_t)g * K + p];
+    part[c * K + p] = s;
+  }
+  __syncthreads();
+  if (tid < K) {
+    double s = 0.0;
+    for (int c = 0; c < C; ++c) s += part[c * K + tid];
+    sum[tid] = s;
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  if (mode == GM_SCREEN) {
+    // a row is valid when its Σ x² is a finite float: NaN, Inf and overflowing rows are out
+    unsigned valid = 0;
+    double ws = 0.0, wall = 0.0;
+    int nvalid = 0;
+    for (int k = 0; k < K; ++k) {
+      const float s = (float)sum[k];
+      wall += (double)w.w[k];
+      if (s - s == 0.f) {
+        valid |= 1u << k;
+        ws += (double)w.w[k];
+        ++nvalid;
+      }
+    }
+    for (int k = 0; k < K; ++k) {
+      const bool ok = (valid >> k) & 1u;
+      if (nvalid == 0) {
+        what[k] = 0.f;
+        coef[k] = wall > 0.0 ? (float)((double)w.w[k] / wall) : 1.f / (float)K;
+      } else {
+        const float wk = !ok ? 0.f : (ws > 0.0 ? w.w[k] : 1.f);
+        what[k] = wk;
+        coef[k] = (float)((double)wk / (ws > 0.0 ? ws : (double)nvalid));
+      }
+    }
+    return;
+  }
+  double o = 0.0, bs = 0.0;
+  bool any = false;
+  for (int k = 0; k < K; ++k) {
+    const double wk = (double)what[k];
+    d[k] = sqrt(sum[k]);
+    const bool fin = d[k] - d[k] == 0.0;
+    beta[k] = fin ? wk / (d[k] > nu ? d[k] : nu) : 0.0;
+    if (wk != 0.0) {
+      any = true;
+      o += wk * d[k];
+    }
+    bs += beta[k];
+  }
+  obj[t] = o;
+  for (int k = 0; k < K; ++k) dist[k] = any ? d[k] : __builtin_nan("");
+  if (bs > 0.0 && bs - bs == 0.0)
+    for (int k = 0; k < K; ++k) coef[k] = (float)(beta[k] / bs);
+}
+
 // SCAFFOLD (Karimireddy et al.) server step in two launches around one all-reduce; float4 body,
 // scalar tail. Sums run in the same k order as the host reference.
 __global__ __launch_bounds__(FL_BLOCK) void k_scaffold_reduce(float* __restrict__ buf, RowPtrs dy, RowPtrs dc, RowW w, int K, int64_t n) {
@@ -694,6 +857,30 @@ void fl_coef_mean(const OutPtrs& outs, int P, const RowPtrs& rows, int K, const 
     default: break;
   }
 }
+void fl_geometric_median(float* work, const RowPtrs& rows, const RowW& w, int K, int iters, double nu, int64_t n, float* coef, double* dist,
+                         double* obj, hipStream_t s) {
+  const unsigned grid = fl_krum_grid(n, K);
+  float* what = work + (int64_t)grid * K;
+  const bool vec = all_aligned16(rows, K, nullptr, 0);
+  const dim3 g(grid), b(FL_BLOCK);
+  // pass -1 is the screen (coefficients 0: the sums are |x_k|^2), passes 0..iters-1 the iterations
+  for (int t = -1; t < iters; ++t) {
+    const float* c = t < 0 ? nullptr : coef;
+    switch (K) {
+#define GM_CASE(KK)                                                                     \
+  case KK:                                                                              \
+    if (vec) hipLaunchKernelGGL((k_gm_dist<KK, true>), g, b, 0, s, work, rows, c, n);   \
+    else hipLaunchKernelGGL((k_gm_dist<KK, false>), g, b, 0, s, work, rows, c, n);      \
+    break;
+      GM_CASE(1) GM_CASE(2) GM_CASE(3) GM_CASE(4) GM_CASE(5) GM_CASE(6) GM_CASE(7) GM_CASE(8)
+      GM_CASE(9) GM_CASE(10) GM_CASE(11) GM_CASE(12) GM_CASE(13) GM_CASE(14) GM_CASE(15) GM_CASE(16)
+#undef GM_CASE
+      default: return;
+    }
+    hipLaunchKernelGGL(k_gm_reweight, dim3(1), dim3(KRUM_SELECT_BLOCK), 0, s, work, (int)grid, K, t < 0 ? GM_SCREEN : GM_ITERATE, t < 0 ? 0 : t, w, nu,
+                       what, coef, dist, obj);
+  }
+}
 void fl_scaffold_reduce(float* buf, const RowPtrs& dy, const RowPtrs& dc, const RowW& w, int K, int64_t n, hipStream_t s) {
   hipLaunchKernelGGL(k_scaffold_reduce, dim3(grid_for(n)), dim3(FL_BLOCK), 0, s, buf, dy, dc, w, K, n);
 }
@@ -716,12 +903,14 @@ void fl_scale_add_noise(float* t, int64_t n, float scale, float sigma, uint64_t 
 extern "C" int myfyp_warm_fl_ops() {
   hipFuncAttributes attr;
   // the robust aggregators' launches of the headline peer count (8) resolve here too, so a first
-  // Krum / trimmed-mean round pays no lookup behind a running epoch
+  // Krum / trimmed-mean / geometric-median round pays no lookup behind a running epoch
   const void* fns[] = {reinterpret_cast<const void*>(&k_weighted_sum),
                        reinterpret_cast<const void*>(&k_trimmed_mean<8>),
                        reinterpret_cast<const void*>(&k_pairwise_sqdist<8, true>),
                        reinterpret_cast<const void*>(&k_krum_select),
-                       reinterpret_cast<const void*>(&k_coef_mean<8, true>)};
+                       reinterpret_cast<const void*>(&k_coef_mean<8, true>),
+                       reinterpret_cast<const void*>(&k_gm_dist<8, true>),
+                       reinterpret_cast<const void*>(&k_gm_reweight)};
   for (const void* fn : fns)
     if (hipFuncGetAttributes(&attr, fn) != hipSuccess) return 1;
   return 0;

@@ -1038,6 +1038,42 @@ int myfyp_krum_multi(const uint64_t* outs, int P, const uint64_t* srcs, const fl
   }
   return 0;
 }
+// Floats of the workspace of myfyp_geomed_multi for n coordinates of K rows.
+int64_t myfyp_geomed_work(int64_t n, int K) { return fl_geomed_work(n, K); }
+// Geometric median (smoothed Weiszfeld, iters steps; device outputs coef[K]: float, dist[K] and
+// obj[iters]: double), then, with P > 0, out rows <- sum_k coef[k] * row k. w: HOST array of the K
+// sample weights. Enqueues only: 2 (iters + 1) + 1 launches.
+int myfyp_geomed_multi(const uint64_t* outs, int P, const uint64_t* srcs, const float* w, int K, int iters, double nu, int64_t n, float* work,
+                       float* coef, double* dist, double* obj, void* stream) {
+  if (!rows_ok(K, "geometric_median") || (P != 0 && !rows_ok(P, "geometric_median outputs"))) return 2;
+  if (iters < 1 || iters > 32 || !(nu > 0.0) || nu - nu != 0.0) {
+    g_last_error = "geometric_median: 1 <= iters <= 32 and a finite nu > 0";
+    return 2;
+  }
+  if (n < 1 || work == nullptr || coef == nullptr || dist == nullptr || obj == nullptr) {
+    g_last_error = "geometric_median: n >= 1 and the work / coef / dist / obj buffers are required";
+    return 2;
+  }
+  RowPtrs rows{};
+  OutPtrs o{};
+  RowW ww{};
+  for (int k = 0; k < K; ++k) {
+    if (!(w[k] >= 0.f) || w[k] - w[k] != 0.f) {
+      g_last_error = "geometric_median: weights are finite and >= 0";
+      return 2;
+    }
+    rows.p[k] = reinterpret_cast<const float*>(srcs[k]);
+    ww.w[k] = w[k];
+  }
+  for (int p = 0; p < P; ++p) o.p[p] = reinterpret_cast<float*>(outs[p]);
+  fl_geometric_median(work, rows, ww, K, iters, nu, n, coef, dist, obj, (hipStream_t)stream);
+  CHECK_HIP(hipGetLastError());
+  if (P > 0) {
+    fl_coef_mean(o, P, rows, K, coef, n, (hipStream_t)stream);
+    CHECK_HIP(hipGetLastError());
+  }
+  return 0;
+}
 int myfyp_scaffold_reduce(float* buf, const uint64_t* dy, const uint64_t* dc, const float* w, int K, int64_t n, void* stream) {
   if (K < 0 || K > 16) {
     g_last_error = "scaffold_reduce supports 0..16 rows";

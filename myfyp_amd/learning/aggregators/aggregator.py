@@ -12,7 +12,8 @@ Collective data plane: an aggregator also exposes ``collective_kind`` which tell
 plane which reduction implements it (``"mean"`` → one weighted all-reduce, ``"neighbor"`` →
 topology mixing, ``"scaffold"`` → packed all-reduce + apply, ``"median"`` / ``"trimmed_mean"`` →
 all-gather + per-coordinate sorting-network kernel, ``"krum"`` → all-gather + distance, selection
-and weighted-mean kernels, ``None`` → host fallback over gathered wire models).
+and weighted-mean kernels, ``"geometric_median"`` → all-gather + distance, reweighting and
+weighted-mean kernels, ``None`` → host fallback over gathered wire models).
 """
 
 from __future__ import annotations

@@ -13,6 +13,9 @@ Ops
 * ``trimmed_mean_into`` — coordinate-wise trimmed mean (the median's sorting network, K ≤ 16)
 * ``krum_into`` — (Multi-)Krum: pairwise squared distances from differences, selection and the
   weighted mean of the chosen rows, all on the device (K ≤ 16); returns ``(dist, score, coef)``
+* ``geometric_median_into`` — geometric median (RFA, smoothed Weiszfeld): a screen of non-finite
+  rows, then per step the distances to the current point and the reweighting, all on the device
+  (K ≤ 16); returns ``(coef, dist, objective)``
 * ``adam_step`` / ``sgd_step`` — fused optimizers over a flat buffer, optionally with the FedProx
   proximal term and the SCAFFOLD control-variate correction fused in (K5, K8, K13)
 * ``scale_add_noise`` — attack injection (sign flip / Gaussian noise, K14)
@@ -34,6 +37,7 @@ __all__ = [
     "coordinate_median",
     "trimmed_mean_into",
     "krum_into",
+    "geometric_median_into",
     "adam_step",
     "sgd_step",
     "scale_add_noise",
@@ -249,6 +253,92 @@ def krum_into(rows: Sequence[torch.Tensor], outs: Sequence[torch.Tensor], weight
         for o in outs:
             o.copy_(mean)
     return dist, score, coef
+
+
+GEOMED_MAX_ITERS = 32
+
+
+def geometric_median_into(rows: Sequence[torch.Tensor], outs: Sequence[torch.Tensor], weights: Sequence[float], iters: int = 3, nu: float = 1e-6):
+    """Geometric median (RFA: Pillutla et al., 2019) of 1-D fp32 rows by ``iters`` smoothed
+    Weiszfeld steps; ``outs[p] = Σ_k coef[k]·rows[k]``. Coefficients are float32 after every step.
+
+    Screen: a row whose ``Σ x²`` is not a finite float32 (NaN, Inf, overflow) is invalid for the
+    call; ``ŵ_k = w_k`` for valid rows (1 where every valid weight is 0), 0 otherwise;
+    ``c = ŵ/Σŵ``. With no valid row ``c = w/Σw`` (or ``1/K``), no step runs, ``dist`` is NaN and
+    the output is the plain mean. Step t: ``r`` the lowest row with ``c_r != 0``,
+    ``z = x_r + Σ_j c_j (x_j − x_r)`` over the rows of coefficient != 0, ``d_k = ‖x_k − z‖``,
+    ``objective[t] = Σ ŵ_k d_k`` over ``ŵ_k != 0``, ``β_k = ŵ_k / max(nu, d_k)`` (0 where ``d_k``
+    is not finite), ``c = β/Σβ`` (kept where ``Σβ`` is 0 or not finite). Returns ``(coef [K]
+    float32, dist [K] float64: the last step's d, objective [iters] float64)`` on the rows' device;
+    ``outs=[]`` gives the weights only.
+
+    On the GPU (K <= 16 rows, <= 16 outputs, which may alias the rows) it is ``2(iters + 1) + 1``
+    launches — ``k_gm_dist<K>`` and ``k_gm_reweight`` for the screen and per step, then
+    ``k_coef_mean<K>`` — that only enqueue. Elsewhere: float64 torch math (the oracle)."""
+    k = len(rows)
+    iters = int(iters)
+    nu = float(nu)
+    if len(weights) != k:
+        raise ValueError(f"{k} rows but {len(weights)} weights")
+    if k < 1:
+        raise ValueError("geometric median of no rows")
+    if not 1 <= iters <= GEOMED_MAX_ITERS:
+        raise ValueError(f"iters must be in 1..{GEOMED_MAX_ITERS}, got {iters}")
+    if not (nu > 0 and nu != float("inf")):
+        raise ValueError(f"nu must be finite and > 0, got {nu}")
+    ws = [float(x) for x in weights]
+    if not all(0 <= x < float("inf") for x in ws):
+        raise ValueError("weights must be finite and >= 0")
+    dev = rows[0].device
+    if _native_rows(rows, outs):
+        lib = _lib()
+        n = rows[0].numel()
+        work = torch.empty(int(lib.myfyp_geomed_work(n, k)), dtype=torch.float32, device=dev)
+        coef = torch.empty(k, dtype=torch.float32, device=dev)
+        dist = torch.empty(k, dtype=torch.float64, device=dev)
+        obj = torch.empty(iters, dtype=torch.float64, device=dev)
+        src, keep_s = _host_ptrs(rows)
+        dst, keep_d = _host_ptrs(outs)
+        w = (ctypes.c_float * k)(*ws)
+        _native.check(lib.myfyp_geomed_multi(dst, len(outs), src, ctypes.cast(w, ctypes.c_void_p), k, iters, nu, n, work.data_ptr(), coef.data_ptr(),
+                                             dist.data_ptr(), obj.data_ptr(), _stream()), "geomed_multi")
+        return coef, dist, obj
+    x = [r.double().reshape(-1) for r in rows]
+    w = torch.tensor(ws, dtype=torch.float64)
+    valid = torch.isfinite(torch.stack([xi.square().sum() for xi in x]).float().cpu())
+    dist = torch.full((k,), float("nan"), dtype=torch.float64)
+    obj = torch.zeros(iters, dtype=torch.float64)
+    if not bool(valid.any()):
+        coef = (w / w.sum() if float(w.sum()) > 0 else torch.full((k,), 1.0 / k, dtype=torch.float64)).float()
+        iters = 0
+    else:
+        what = torch.where(valid, w, torch.zeros_like(w))
+        if float(what.sum()) == 0:
+            what = valid.double()
+        coef = (what / what.sum()).float()
+    for t in range(iters):
+        c = coef.double().tolist()
+        nz = [j for j in range(k) if c[j] != 0]
+        xr = x[nz[0]]
+        m = torch.zeros_like(xr)
+        for j in nz:
+            m += c[j] * (x[j] - xr)
+        dist = torch.stack([((xi - xr) - m).square().sum().sqrt() for xi in x]).cpu()
+        live = what != 0
+        obj[t] = (what[live] * dist[live]).sum()
+        beta = torch.where(torch.isfinite(dist), what / dist.clamp(min=nu), torch.zeros_like(what))
+        bs = float(beta.sum())
+        if bs > 0 and bs != float("inf"):
+            coef = (beta / bs).float()
+    if outs:
+        c = coef.double().tolist()
+        mean = torch.zeros_like(x[0])
+        for j in range(k):
+            if c[j] != 0:
+                mean += c[j] * x[j]
+        for o in outs:
+            o.copy_(mean)
+    return coef.to(dev), dist.to(dev), obj.to(dev)
 
 
 def scaffold_reduce(buf: torch.Tensor, dys: Sequence[torch.Tensor], dcs: Sequence[torch.Tensor], weights: Sequence[float]) -> None:

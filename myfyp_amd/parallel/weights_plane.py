@@ -730,7 +730,7 @@ def _mesh_neighbors(fed: Federation, peers, index, w, local, learners) -> None:
 
 
 # aggregator kinds reduced on the device (no wire models, no host copies)
-DEVICE_KINDS = ("mean", "neighbor", "scaffold", "median", "krum", "trimmed_mean")
+DEVICE_KINDS = ("mean", "neighbor", "scaffold", "median", "krum", "trimmed_mean", "geometric_median")
 
 
 def _scaffold_cb(learner):
@@ -938,9 +938,9 @@ def _median(fed: Federation, arrived: Dict[str, Tuple[float, Any]]) -> None:
 
 
 # ---------------------------------------------------------------------------------------------
-# robust aggregation: coordinate-wise trimmed mean and (Multi-)Krum
+# robust aggregation: coordinate-wise trimmed mean, (Multi-)Krum and the geometric median
 # ---------------------------------------------------------------------------------------------
-ROBUST_MAX_ROWS = 16  # rows the device kernels take (ops.trimmed_mean_into / ops.krum_into)
+ROBUST_MAX_ROWS = 16  # rows the device kernels take (ops.trimmed_mean_into / krum_into / geometric_median_into)
 
 
 @traced("aggregate_trimmed_mean")
@@ -969,6 +969,21 @@ def aggregate_krum(fed: Federation, arrived: Dict[str, Tuple[float, Any]], aggre
     fed.record("aggregate", time.perf_counter() - t0)
 
 
+@traced("aggregate_geometric_median")
+def aggregate_geometric_median(fed: Federation, arrived: Dict[str, Tuple[float, Any]], aggregator) -> None:
+    """Geometric median of the trainers' models on the device (host math:
+    ``GeometricMedian.aggregate``): the all-gather of :func:`aggregate_median`, then
+    ``ops.geometric_median_into`` — the screen, ``aggregator.iters`` smoothed Weiszfeld steps and
+    the weighted mean written into every local peer, no coefficient leaving the device on the
+    round's path. Every rank reduces the same gathered buffer with the same grid, so all of them
+    reach the same coefficients, bit for bit. Afterwards every local node's aggregator carries
+    ``last_weights = (trainer addresses in row order, coef)``; ``coef`` is the device tensor
+    (reading it is the caller's synchronisation), small for a down-weighted peer."""
+    t0 = time.perf_counter()
+    fed.run_aggregation(lambda: _robust(fed, arrived, aggregator, "geometric_median"))
+    fed.record("aggregate", time.perf_counter() - t0)
+
+
 def _trim_count(aggregator, k: int) -> int:
     trim = int(np.floor(aggregator.beta * k))
     if 2 * trim >= k:
@@ -977,11 +992,13 @@ def _trim_count(aggregator, k: int) -> int:
 
 
 def _robust_into(kind: str, aggregator, rows, outs, ws):
-    """The device op of ``kind``; Krum returns its ``coef`` device tensor."""
+    """The device op of ``kind``; Krum and the geometric median return their ``coef`` device tensor."""
     with torch.no_grad():
         if kind == "trimmed_mean":
             ops.trimmed_mean_into(rows, outs, _trim_count(aggregator, len(rows)))
             return None
+        if kind == "geometric_median":
+            return ops.geometric_median_into(rows, outs, ws, aggregator.iters, aggregator.nu)[0]
         return ops.krum_into(rows, outs, ws, aggregator.f, aggregator.m)[2]
 
 
@@ -995,11 +1012,13 @@ def _row_fns(learners, kind: str):
     the floating buffers ``_unpack_into`` takes back). The host ``Krum`` measures every tensor of
     ``get_parameters()`` — the whole ``state_dict``, BatchNorm's integer ``num_batches_tracked``
     included — so the Krum row carries those counters too, behind everything that is unpacked: the
-    device and the host then score the same vector and select the same peers."""
-    live = all(len(state_tensors(lr)) == 1 and not (kind == "krum" and _int_buffers(lr)) for lr in learners)
+    device and the host then score the same vector and select the same peers. The geometric median
+    measures distances too, and takes the same rows."""
+    whole = kind in ("krum", "geometric_median")
+    live = all(len(state_tensors(lr)) == 1 and not (whole and _int_buffers(lr)) for lr in learners)
     if live:
         return True, lambda lr: lr.flat_params()
-    if kind == "krum":
+    if whole:
         return False, lambda lr: torch.cat([_pack(lr)] + [b.detach().reshape(-1).float() for b in _int_buffers(lr)])
     return False, _pack
 
@@ -1007,10 +1026,12 @@ def _row_fns(learners, kind: str):
 def _publish_selection(fed: Federation, addrs, aggregator, order, coef) -> None:
     if coef is None:
         return
-    aggregator.last_selection = (list(order), coef)
+    # Krum publishes a selection, the geometric median its weights
+    attr = "last_weights" if getattr(aggregator, "collective_kind", None) == "geometric_median" else "last_selection"
+    setattr(aggregator, attr, (list(order), coef))
     for a in addrs:
         if a in fed.local_nodes:
-            fed.local_nodes[a].aggregator.last_selection = (list(order), coef)
+            setattr(fed.local_nodes[a].aggregator, attr, (list(order), coef))
 
 
 def _robust(fed: Federation, arrived: Dict[str, Tuple[float, Any]], aggregator, kind: str) -> None:
@@ -1059,7 +1080,7 @@ def _robust(fed: Federation, arrived: Dict[str, Tuple[float, Any]], aggregator, 
 
 
 def _mesh_robust(fed: Federation, arrived: Dict[str, Tuple[float, Any]], aggregator, kind: str) -> None:
-    """Trimmed mean / Krum over a device mesh, in the manner of ``_mesh_median``: every device
+    """Trimmed mean / Krum / geometric median over a device mesh, in the manner of ``_mesh_median``: every device
     packs its trainers' rows ([k_max, n], zero-padded), ONE mesh all-gather, then per device the op
     into a result vector unpacked into its peers. Every device reduces the same gathered rows in the
     same order, so a Krum selection is the same on all of them."""
