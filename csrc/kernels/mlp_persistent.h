@@ -41,6 +41,8 @@ struct MLPPersistF32Bufs {
   int plain;        // plain_ok if this gang does, else 0 (set in the kernel); cross-XCD K split: within a group
   int plain_x;      // hand-offs between the groups of a gang (set in the kernel: plain, or 0 for a cross-XCD K split)
   int c2_straight;  // layout 1, K split 1: owners may take C2's straight-line body (set at launch: MYFYP_F32_C2_STRAIGHT)
+  int k24;          // ... and the wave that owns K step 24 keeps its state in registers over the step loop (set at launch
+                    // where it applies: MYFYP_F32_K24; the launch then takes the K24 instantiation)
 };
 
 int mlp_plain_pub_mode();  // single-XCD hand-off mode of the persistent kernels (MYFYP_F32_PLAIN_PUB / mlp_set_plain_pub)

@@ -70,11 +70,12 @@ void mlp_f32v2_launch(const MLPArgs& a, const MLPPersistF32Bufs& pb, hipStream_t
 
 // Optional phase timestamps (build with -DMLP_STAMPS): peer 0's owner 0 (role 0) and head 0 (role 1),
 // steps < 128, read with mlp_debug_persistent_f32_stamps (wall_clock64 ticks, 100 MHz). Owner slot 8
-// is wave 1's end of C2 (fused loop), every other stamp is thread 0's.
+// is wave 1's end of C2 (fused loop) and slots 10..17 are the same point of waves 0..7 (lane 0 of
+// each), every other stamp is thread 0's.
 // Epoch-level stamps of peer 0's owner 0: [0] kernel entry, [1] first step start, [2] gang commit
 // passed, [3] write-back done (mlp_debug_persistent_f32_epoch_stamps).
 #ifdef MLP_STAMPS
-__device__ unsigned long long g_p32_stamps[2][128][10];
+__device__ unsigned long long g_p32_stamps[2][128][18];
 __device__ unsigned long long g_p32_epoch[4];
 #define P32_STAMP(role, t, i)                                                                    \
   do {                                                                                           \
@@ -88,6 +89,12 @@ __device__ unsigned long long g_p32_epoch[4];
 #define P32_STAMP_W1(t, i)                                                                   \
   do {                                                                                       \
     if (p == 0 && threadIdx.x == 64 && (t) < 128) g_p32_stamps[0][t][i] = wall_clock64(); \
+  } while (0)
+// owner slots 10..17: the end of C2 as lane 0 of each wave sees it (where the waves arrive at the
+// step's last barrier)
+#define P32_STAMP_WV(t, i0)                                                                                         \
+  do {                                                                                                              \
+    if (p == 0 && (threadIdx.x & 63) == 0 && (t) < 128) g_p32_stamps[0][t][(i0) + (threadIdx.x >> 6)] = wall_clock64(); \
   } while (0)
 extern "C" int mlp_debug_persistent_f32_stamps(void* out) {
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_p32_stamps), sizeof(g_p32_stamps)) == hipSuccess ? 0 : 1;
@@ -104,6 +111,9 @@ extern "C" int mlp_debug_persistent_f32_epoch_stamps(void* out) {
   } while (0)
 #define P32_STAMP_W1(t, i) \
   do {                     \
+  } while (0)
+#define P32_STAMP_WV(t, i0) \
+  do {                      \
   } while (0)
 #endif
 
@@ -337,11 +347,12 @@ __device__ __forceinline__ bool gang_commit(const MLPArgs& a, const MLPPersistF3
   return persist::wg_wait(pb.flags, FPP, p, FD, NR, pb.fbase + DONE_MARK, pb.err, sOk);
 }
 
-template <int BP, bool ADAM, bool EXTRA, int KS, bool RH, bool FUSE = false>
+template <int BP, bool ADAM, bool EXTRA, int KS, bool RH, bool FUSE = false, int K24 = 0>
 __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, int g, char* smem) {
   // FUSE: the forward of step t + 1 is accumulated inside C2 of step t, K step by K step, by the wave
   // that has just updated that K step's weights and staged its columns of the next batch
   static_assert(!FUSE || (KS == 1 && !RH && !EXTRA), "fused forward: layout 1, K split 1, no extra term");
+  static_assert(K24 == 0 || FUSE, "K step 24 in registers: fused forward only");
   constexpr int MT = BP / 16;
   constexpr int RQ = rq_of(KS);
   constexpr int XPT = BP / 4;  // 16-byte X chunks per lane: 4 K steps x BP rows x 4 chunks / 64 lanes
@@ -374,6 +385,8 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
   // ---- resident W1 rows: wave w owns K steps w, w+8, w+16 (registers) and w+24 (LDS), κ slot
   //      order; the slot of column D0 holds b1
   float w1[RQ][8], m1[RQ][8], v1[RQ][8], e1[RQ][8];
+  // K step 24's state while wave 0 keeps it in registers over the step loop (the K24 instantiations, below)
+  float w1x[8], m1x[8], v1x[8], e1x[8];
   const int orow = NCG * cg + c;
 #pragma unroll
   for (int q = 0; q < RQ + 1; ++q) {
@@ -487,8 +500,8 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
   // forward contribution of this wave's K step q (slot q) to the H1 slice, with the weights as they
   // are now and the batch tile currently staged in LDS. The LDS-resident K step (q == RQ, KS = 1:
   // K step 24, D0 > 767) is wave 0's. chk = false (C2's straight body): the caller knows the K step
-  // exists, no test.
-  auto fwd_kstep = [&](int q, f32x4(&acc)[MT], bool chk = true) __attribute__((always_inline)) {
+  // exists, no test. rx (the K24 instantiations): the LDS-resident K step's weights are in w1x, not in sW1x.
+  auto fwd_kstep = [&](int q, f32x4(&acc)[MT], bool chk = true, bool rx = false) __attribute__((always_inline)) {
     const int s = wave + 8 * q;
     if (chk && s >= KS1) return;
     // lane coordinates laundered per K step: the compiler would otherwise hoist every LDS address
@@ -498,7 +511,7 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
     const int hq = lq >> 4, cq = lq & 15;
     float wq[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) wq[j] = q < RQ ? w1[q < RQ ? q : 0][j] : sW1x[cq * 32 + kappa(hq, j)];
+    for (int j = 0; j < 8; ++j) wq[j] = q < RQ ? w1[q < RQ ? q : 0][j] : rx ? w1x[j] : sW1x[cq * 32 + kappa(hq, j)];
     bf16x8 bh, bm, bl;
     split3(wq, bh, bm, bl);
     if constexpr (FUSE) {
@@ -620,10 +633,45 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
   // the same barriers in the same order. The `body` loop stays where there is no straight body (one
   // trip): with it the loop-carried Adam state is no longer copied around the step loop's back-edge
   // (-30 to -70 VGPRs in every Adam instantiation, profiles/r9_c2_straight/isa.md).
+  // K24 (an instantiation of its own, fused forward only; MYFYP_F32_K24): the launch takes it only
+  // where every wave runs the straight body and K step 24 exists (switch on, D0 >= 768), so it has no
+  // guarded loop. Its two loops are both straight: loop 0 for the waves without a K step 24 (no code
+  // for it at all), loop 1 for the wave that owns it (wave 0), which takes that K step's state from
+  // sW1x into registers before the step loop and returns it after, and runs the K step from them as a
+  // fourth register-resident one: no test, no `more` guard and no per-step LDS round trip of the state
+  // (8 float4 loads, 6 float4 stores and the forward's 8 scalar reads per lane and step). Nobody else
+  // reads sW1x in between: the write-back after gang_commit is that wave's own. Same operations on
+  // the same values: same bits. As a third loop beside the guarded and the straight one, chosen by a
+  // kernel argument, it made the allocator spill in the guarded loop (Adam, Bpad 64: 22 VGPRs, 92 B of
+  // scratch; SGD: 43); this way every kernel keeps two loops.
+  constexpr bool KI = SI && FUSE && K24 == 1;
+  if (KI && !(straight && 8 * RQ < KS1)) return;  // (never taken: see mlp_launch_persistent_f32_epoch)
 #pragma unroll
   for (int body = 0; body < (SI ? 2 : 1); ++body) {
-  const bool ST = SI && body == 1;
-  if (SI && straight != ST) continue;
+  const bool ST = SI && (KI || body == 1);
+  const bool KR = KI && body == 1;
+  constexpr int QN = KS == 1 ? RQ + 1 : RQ;  // K steps of a wave, the LDS-resident one included
+  const int qn = KI && !KR ? RQ : QN;
+  if (SI && (KI ? wave + 8 * RQ < KS1 : straight) != (body == 1)) continue;
+  if (KR) {
+    int lk = lane;
+    asm volatile("" : "+v"(lk));
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+      const int off = (lk & 15) * 32 + 16 * half + 4 * (lk >> 4);
+      // (SGD never touches v: its plane stays in LDS as it is)
+      const float4 w = *reinterpret_cast<const float4*>(sW1x + off), m = *reinterpret_cast<const float4*>(sW1x + 512 + off),
+                   v = ADAM ? *reinterpret_cast<const float4*>(sW1x + 1024 + off) : float4{0.f, 0.f, 0.f, 0.f};
+      const float wa[4] = {w.x, w.y, w.z, w.w}, ma[4] = {m.x, m.y, m.z, m.w}, va[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        w1x[4 * half + i] = wa[i];
+        m1x[4 * half + i] = ma[i];
+        v1x[4 * half + i] = va[i];
+        e1x[4 * half + i] = 0.f;  // (no extra term where this body exists)
+      }
+    }
+  }
   for (int t = 0; t < nsteps; ++t) {
     int tv = tid;  // per-iteration opaque thread index (addresses re-derived each step: VGPR pressure)
     asm volatile("" : "+v"(tv));
@@ -830,9 +878,13 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
       // step: gang_commit touches sOk only, the write-back reads the weight registers and sW1x, and
       // the debug replica update reads sH1 and the dH2 exchange buffer. The LDS-resident K step
       // (q == RQ) keeps its wave-uniform test in both bodies and has the branch-free stores in both.
+      // The K24 instantiation: no such K step in loop 0; in loop 1 (KR) it is one more straight K step,
+      // its state in w1x / m1x / v1x.
 #pragma unroll
-      for (int q = 0; q < (KS == 1 ? RQ + 1 : RQ); ++q) {
-        const bool STq = ST && q < RQ;  // the LDS-resident K step runs in its guarded form in either body
+      for (int q = 0; q < QN; ++q) {
+        if (q >= qn) continue;
+        // the LDS-resident K step runs in its guarded form in either body (KR: straight, from registers)
+        const bool STq = ST && (q < RQ || KR);
         // wave w owns K step w + 8q, both 16-column halves (tt = 0, 1); q == RQ (KS = 1): the
         // LDS-resident K step, wave 0's
         const int s = wave + 8 * q;
@@ -873,8 +925,20 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
             if (q < RQ) {
               const int qq = q < RQ ? q : 0;
 #pragma unroll
-              for (int i = 0; i < 4; ++i)
+              for (int i = 0; i < 4; ++i) {
                 upd32<ADAM, EXTRA>(o, acc[i], w1[qq][4 * tt + i], m1[qq][4 * tt + i], v1[qq][4 * tt + i], e1[qq][4 * tt + i], lr_t, inv_bc2, wdmu);
+                if (!ADAM && KI) asm("" : "+v"(w1[qq][4 * tt + i]), "+v"(m1[qq][4 * tt + i]));  // (see K step 24, below)
+              }
+            } else if (KR) {  // K step 24, register-resident over this step loop
+#pragma unroll
+              for (int i = 0; i < 4; ++i) {
+                upd32<ADAM, EXTRA>(o, acc[i], w1x[4 * tt + i], m1x[4 * tt + i], v1x[4 * tt + i], e1x[4 * tt + i], lr_t, inv_bc2, wdmu);
+                // SGD: the compiler packs the independent updates into v_pk_fma_f32, and the loop-carried
+                // w / m then live in 64-bit tuples that are copied around the back-edge in a second
+                // register set (20-46 VGPRs spilled with K step 24 added). Laundered per element they
+                // stay scalar: 194 VGPRs at Bpad 64, no scratch (profiles/r10_k24_balance/registers.txt)
+                if (!ADAM) asm("" : "+v"(w1x[4 * tt + i]), "+v"(m1x[4 * tt + i]));
+              }
             } else {  // the LDS-resident K step
               const int off = (lq & 15) * 32 + 16 * tt + 4 * (lq >> 4);
               float4 w = *reinterpret_cast<float4*>(sW1x + off), m = *reinterpret_cast<float4*>(sW1x + 512 + off),
@@ -908,9 +972,9 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
         // fused loop: the K step's weights are updated and its columns of X(t + 1) staged, both by
         // this wave (its own registers and LDS writes, which complete in order): no barrier
         if constexpr (FUSE) {
-          if (q + 1 < (KS == 1 ? RQ + 1 : RQ)) xq_load(q + 1, !STq);
+          if (q + 1 < qn) xq_load(q + 1, !STq);
           if (STq)
-            fwd_kstep(q, accF, false);
+            fwd_kstep(q, accF, false, KR);
           else if (more)
             fwd_kstep(q, accF);
         }
@@ -918,6 +982,7 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
       if constexpr (FUSE) {
         if (g == 0) P32_STAMP(0, t, 6);
         if (g == 0) P32_STAMP_W1(t, 8);
+        if (g == 0) P32_STAMP_WV(t, 10);
         // H1(t + 1): sRed is free (C1's partials were consumed before C1's last barrier), and so is
         // the exchange slab of parity (t + 1) & 1 (the heads read H1(t - 1) before they produced
         // dH2(t)). The reduction's barrier is the one that ends the step.
@@ -933,6 +998,17 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
       if (g == 0) P32_STAMP(0, t, 6);
     }
     }  // step loop (kept at its indentation inside the body loop)
+  if (KR) {  // K step 24's state back to sW1x, where the write-back below reads it (this wave's own reads)
+    int lk = lane;
+    asm volatile("" : "+v"(lk));
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+      const int off = (lk & 15) * 32 + 16 * half + 4 * (lk >> 4), j0 = 4 * half;
+      *reinterpret_cast<float4*>(sW1x + off) = float4{w1x[j0], w1x[j0 + 1], w1x[j0 + 2], w1x[j0 + 3]};
+      *reinterpret_cast<float4*>(sW1x + 512 + off) = float4{m1x[j0], m1x[j0 + 1], m1x[j0 + 2], m1x[j0 + 3]};
+      if (ADAM) *reinterpret_cast<float4*>(sW1x + 1024 + off) = float4{v1x[j0], v1x[j0 + 1], v1x[j0 + 2], v1x[j0 + 3]};
+    }
+  }
   }    // body loop
 
   if (!gang_commit<KS, RH, BP>(a, pb, p, g, sOk)) return;
@@ -1705,7 +1781,7 @@ __device__ void headr32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
 // flags offset by RETRY_BASE (the aborted attempt's flag values are all smaller), and on success
 // sets err[p] = 2 ("recovered"). Gangs are independent: one peer's give-up never aborts another.
 
-template <int BP, bool ADAM, bool EXTRA, int KS, bool RH = false, bool FUSE = false>
+template <int BP, bool ADAM, bool EXTRA, int KS, bool RH = false, bool FUSE = false, int K24 = 0>
 __global__ __launch_bounds__(NT) void mlp_persistent_f32_epoch(MLPArgs a, MLPPersistF32Bufs pb, int p_base, int attempt) {
   extern __shared__ __attribute__((aligned(16))) char smem_p32[];
   constexpr int PPL = ppl_of(KS, RH);
@@ -1773,7 +1849,7 @@ __global__ __launch_bounds__(NT) void mlp_persistent_f32_epoch(MLPArgs a, MLPPer
     if (role == 0 && threadIdx.x == 0 && p < 64) g_plain_seen[p] = pb.plain;
   }
   if (role < ng_of(KS))
-    owner32<BP, ADAM, EXTRA, KS, RH, FUSE>(a, pb, p, role, smem_p32);
+    owner32<BP, ADAM, EXTRA, KS, RH, FUSE, K24>(a, pb, p, role, smem_p32);
   else if (RH)
     headr32<BP, ADAM, EXTRA, KS>(a, pb, p, role - ng_of(KS), smem_p32);
   else
@@ -1996,9 +2072,9 @@ bool v3_supported(const MLPArgs& a) {
   return persistent_f32_lds_ks(a, 1, true) <= 160 * 1024;
 }
 
-template <int BP, bool ADAM, bool EXTRA, int KS, bool RH = false, bool FUSE = false>
+template <int BP, bool ADAM, bool EXTRA, int KS, bool RH = false, bool FUSE = false, int K24 = 0>
 const void* f32_fn() {
-  return (const void*)mlp_persistent_f32_epoch<BP, ADAM, EXTRA, KS, RH, FUSE>;
+  return (const void*)mlp_persistent_f32_epoch<BP, ADAM, EXTRA, KS, RH, FUSE, K24>;
 }
 // the fused forward (owner32's FUSE) is instantiated for layout 1 at K split 1 without an extra term
 __host__ __device__ constexpr bool fuse_inst(int KS, bool RH) { return KS == 1 && !RH; }
@@ -2011,7 +2087,8 @@ hipError_t prepare_f32_bp(int lds) {
     if (e != hipSuccess) return e;
   }
   if constexpr (fuse_inst(KS, RH)) {
-    for (const void* fn : {f32_fn<BP, true, false, KS, RH, true>(), f32_fn<BP, false, false, KS, RH, true>()}) {
+    for (const void* fn : {f32_fn<BP, true, false, KS, RH, true>(), f32_fn<BP, false, false, KS, RH, true>(),
+                           f32_fn<BP, true, false, KS, RH, true, 1>(), f32_fn<BP, false, false, KS, RH, true, 1>()}) {
       const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
       if (e != hipSuccess) return e;
     }
@@ -2024,6 +2101,11 @@ void launch_f32_bp(const MLPArgs& a, const MLPPersistF32Bufs& pb, hipStream_t s,
   const bool adam = a.opt.kind == 0;
   const bool extra = a.anchor != nullptr || a.cg != nullptr;
   if constexpr (fuse_inst(KS, RH)) {
+    if (fuse && !extra && pb.k24 == 1) {  // K step 24 register-resident (set by the launch where it applies)
+      if (adam) hipLaunchKernelGGL((mlp_persistent_f32_epoch<BP, true, false, KS, RH, true, 1>), grid, block, lds, s, a, pb, p_base, attempt);
+      else hipLaunchKernelGGL((mlp_persistent_f32_epoch<BP, false, false, KS, RH, true, 1>), grid, block, lds, s, a, pb, p_base, attempt);
+      return;
+    }
     if (fuse && !extra) {
       if (adam) hipLaunchKernelGGL((mlp_persistent_f32_epoch<BP, true, false, KS, RH, true>), grid, block, lds, s, a, pb, p_base, attempt);
       else hipLaunchKernelGGL((mlp_persistent_f32_epoch<BP, false, false, KS, RH, true>), grid, block, lds, s, a, pb, p_base, attempt);
@@ -2209,6 +2291,28 @@ static int f32_c2_straight_mode() {
 extern "C" int mlp_set_f32_c2_straight(int mode) { return g_straight_override.exchange(mode < 0 ? -1 : mode); }
 extern "C" int mlp_f32_c2_straight_last() { return g_straight_last.load(std::memory_order_relaxed); }
 
+// MYFYP_F32_K24: 1 (default) the wave that owns K step 24 (wave 0 of an owner, D0 >= 768) keeps that K
+// step's weights and moments in registers over the step loop and runs it inside C2's straight block,
+// 0 it stays LDS-resident in its guarded form (A/B; same bits either way); mlp_set_f32_k24 overrides
+// it (tests; -1: back to the environment). Values above 1 are taken as 1. It needs the fused forward
+// and the straight body; where it applies the launch sets pb.k24 and takes the K24 instantiation
+// (the mode as a kernel argument spilled: owner32). mlp_f32_k24_last: what the last
+// layout-1 epoch launch took: 1 if the switch, the fused forward and the straight body were on and
+// D0 has a K step 24, else 0 (-1: none yet).
+static std::atomic<int> g_k24_override{-1};
+static std::atomic<int> g_k24_last{-1};
+static int f32_k24_mode() {
+  const int o = g_k24_override.load(std::memory_order_relaxed);
+  if (o >= 0) return o;
+  static const int v = [] {
+    const char* e = getenv("MYFYP_F32_K24");
+    return e != nullptr ? atoi(e) : 1;
+  }();
+  return v;
+}
+extern "C" int mlp_set_f32_k24(int mode) { return g_k24_override.exchange(mode < 0 ? -1 : mode); }
+extern "C" int mlp_f32_k24_last() { return g_k24_last.load(std::memory_order_relaxed); }
+
 hipError_t mlp_launch_persistent_f32_epoch(const MLPArgs& a, const MLPPersistF32Bufs& pb_in, hipStream_t s, bool zero_flags, const int* active) {
   MLPPersistF32Bufs pb = pb_in;
   pb.plain_ok = mlp_plain_pub_mode();
@@ -2228,7 +2332,10 @@ hipError_t mlp_launch_persistent_f32_epoch(const MLPArgs& a, const MLPPersistF32
   const bool fuse = f32_fwd_fuse_mode() != 0 && fuse_inst(KS, rh) && a.anchor == nullptr && a.cg == nullptr;
   g_fuse_last.store(fuse ? 1 : 0, std::memory_order_relaxed);
   pb.c2_straight = f32_c2_straight_mode() != 0 ? 1 : 0;
-  g_straight_last.store(pb.c2_straight && !rh && KS == 1 && 7 + 8 * (rq_of(1) - 1) < ks1_of(a.D0) ? 1 : 0, std::memory_order_relaxed);
+  const bool straight_all = pb.c2_straight && !rh && KS == 1 && 7 + 8 * (rq_of(1) - 1) < ks1_of(a.D0);
+  g_straight_last.store(straight_all ? 1 : 0, std::memory_order_relaxed);
+  pb.k24 = f32_k24_mode() > 0 && fuse && straight_all && 8 * rq_of(1) < ks1_of(a.D0) ? 1 : 0;
+  g_k24_last.store(pb.k24, std::memory_order_relaxed);
   // groups of ppl peers: one launch each (a launch's gangs must all be co-resident), then the
   // recovery launches (attempt 1): a no-op exit for every gang that did not give up
   // (a group with no active peer is not launched: at one peer per device and K split 8 the other

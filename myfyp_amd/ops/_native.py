@@ -112,6 +112,8 @@ _SIGNATURES = {
     "mlp_f32_fwd_fuse_last": (c_int, []),  # path of the last fp32 layout-1/3 epoch launch (1 fused, 0 separate)
     "mlp_set_f32_c2_straight": (c_int, [c_int]),  # owners' straight-line C2 body: 1 / 0 (-1: MYFYP_F32_C2_STRAIGHT)
     "mlp_f32_c2_straight_last": (c_int, []),  # 1: the last fp32 layout-1 epoch launch could take it in every wave
+    "mlp_set_f32_k24": (c_int, [c_int]),  # K step 24 register-resident on its wave: 1 / 0 (-1: MYFYP_F32_K24)
+    "mlp_f32_k24_last": (c_int, []),  # 1: the last fp32 layout-1 epoch launch ran K step 24 from registers
     "mlp_debug_stamps": (c_int, [c_void_p]),  # only in the -DMLP_STAMPS diagnostics build
     "mlp_debug_persistent_f32_stamps": (c_int, [c_void_p]),  # likewise
 }

@@ -34,7 +34,7 @@ for it in range(3):
     [t.start() for t in ths]
     [t.join() for t in ths]
 torch.cuda.synchronize()
-st = np.zeros((2, 128, 10), dtype=np.uint64)
+st = np.zeros((2, 128, 18), dtype=np.uint64)  # g_p32_stamps[2][128][18]
 ep = np.zeros(4, dtype=np.uint64)
 assert lib.mlp_debug_persistent_f32_stamps(st.ctypes.data) == 0
 assert lib.mlp_debug_persistent_f32_epoch_stamps(ep.ctypes.data) == 0

@@ -37,7 +37,7 @@ for it in range(2):
     [t.start() for t in ths]
     [t.join() for t in ths]
 torch.cuda.synchronize()
-st = np.zeros((2, 128, 10), dtype=np.uint64)  # g_p32_stamps[2][128][10]
+st = np.zeros((2, 128, 18), dtype=np.uint64)  # g_p32_stamps[2][128][18]
 assert lib.mlp_debug_persistent_f32_stamps(st.ctypes.data) == 0
 st = st.astype(np.int64)
 fuse_last = getattr(lib, "mlp_f32_fwd_fuse_last", None)
@@ -77,6 +77,14 @@ if fused:
     w1 = np.array([[(st[0, t, 8] - st[0, t, 5]) / 100.0, (st[0, t, 6] - st[0, t, 8]) / 100.0] for t in range(2, 14)])
     print("C2 + fused fwd of wave 1 (us):", " ".join(f"{x:5.2f}" for x in w1[:, 0]), "| median", f"{np.median(w1[:, 0]):5.2f}")
     print("wave 0 ends C2 after wave 1 by (us):", " ".join(f"{x:5.2f}" for x in w1[:, 1]), "| median", f"{np.median(w1[:, 1]):5.2f}")
+    # owner slots 10..17: the same point of every wave (lane 0 of waves 0..7), from the end of C1
+    wv = np.array([[(st[0, t, 10 + w] - st[0, t, 5]) / 100.0 for w in range(8)] for t in range(2, 14)])
+    print("C2 + fused fwd per wave, medians (us): " + " ".join(f"w{w} {np.median(wv[:, w]):5.2f}" for w in range(8)))
+    print("last wave ends C2 (us after C1), median:", f"{np.median(wv.max(axis=1)):5.2f}", "| wave 0 after the last of waves 1..7, median:",
+          f"{np.median(wv[:, 0] - wv[:, 1:].max(axis=1)):5.2f}")
+    k24_last = getattr(lib, "mlp_f32_k24_last", None)
+    if k24_last is not None:
+        print("K step 24:", "registers (MYFYP_F32_K24=1)" if k24_last() == 1 else "LDS-resident, guarded")
 print("owner H1 published -> head H1 seen (us; fused: negative while the head is still in step t - 1):", [round((st[1, t, 1] - st[0, t, 2]) / 100.0, 2) for t in range(2, 10)])
 print("head dH2 published -> owner dH2 seen (us):", [round((st[0, t, 4] - st[1, t, 7]) / 100.0, 2) for t in range(2, 10)])
 print("head PL published -> head PL all seen (us):", [round((st[1, t, 5] - st[1, t, 4]) / 100.0, 2) for t in range(2, 10)])
