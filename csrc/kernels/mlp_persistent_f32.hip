@@ -880,6 +880,26 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
       // (q == RQ) keeps its wave-uniform test in both bodies and has the branch-free stores in both.
       // The K24 instantiation: no such K step in loop 0; in loop 1 (KR) it is one more straight K step,
       // its state in w1x / m1x / v1x.
+      // Fused forward, straight body: the dH1 split fragments (hi / mid / lo x BP / 32 per lane) are the
+      // same for every K step and both column halves, so they are read once per step, ahead of the
+      // K-step loop, and every straight K step's mfma3 takes them from registers (6 ds_read_b128 per
+      // lane and step at Bpad 64 instead of 18 or 24, and no LDS wait in front of the dW1 MFMAs but
+      // the X fragments'). Nothing writes sD3 between C1's last barrier and the end of C2. Same
+      // values into the same MFMAs in the same order: same bits. The guarded body and the guarded
+      // LDS-resident K step keep their per-K-step reads (profiles/r11_c2_pipeline).
+      constexpr int DFR = FUSE ? BP / 32 : 1;
+      bf16x8 dfr[3][DFR];
+      if (FUSE && ST) {
+        int lq = lane;
+        asm volatile("" : "+v"(lq));
+        const bf16* dfrag = sD3 + (lq & 15) * LDT + 8 * (lq >> 4);
+#pragma unroll
+        for (int kb = 0; kb < DFR; ++kb) {
+          dfr[0][kb] = ld8(dfrag + 32 * kb);
+          dfr[1][kb] = ld8(dfrag + 16 * LDT + 32 * kb);
+          dfr[2][kb] = ld8(dfrag + 32 * LDT + 32 * kb);
+        }
+      }
 #pragma unroll
       for (int q = 0; q < QN; ++q) {
         if (q >= qn) continue;
@@ -919,9 +939,13 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
           for (int tt = 0; tt < 2; ++tt) {
             f32x4 acc = zero4();  // C[k = 32s + 16tt + 4h + i][o1 = c]
 #pragma unroll
-            for (int kb = 0; kb < BP / 32; ++kb)
-              acc = mfma3(frag_b_tr_x(sX, LDX, 32 * kb, s, tt, lq), ld8(dfrag + 32 * kb), ld8(dfrag + 16 * LDT + 32 * kb),
-                          ld8(dfrag + 32 * LDT + 32 * kb), acc);
+            for (int kb = 0; kb < BP / 32; ++kb) {
+              if (FUSE && STq)  // the fragments read ahead of the loop
+                acc = mfma3(frag_b_tr_x(sX, LDX, 32 * kb, s, tt, lq), dfr[0][FUSE ? kb : 0], dfr[1][FUSE ? kb : 0], dfr[2][FUSE ? kb : 0], acc);
+              else
+                acc = mfma3(frag_b_tr_x(sX, LDX, 32 * kb, s, tt, lq), ld8(dfrag + 32 * kb), ld8(dfrag + 16 * LDT + 32 * kb),
+                            ld8(dfrag + 32 * LDT + 32 * kb), acc);
+            }
             if (q < RQ) {
               const int qq = q < RQ ? q : 0;
 #pragma unroll
