@@ -1,13 +1,14 @@
-"""Krum / TrimmedMean / GeometricMedian aggregation on the collective plane: device path against the generic path.
+"""Krum / TrimmedMean / GeometricMedian / Bulyan aggregation on the collective plane: device path against the generic path.
 
     python benchmarks/bench_robust_agg.py                      # MLP (n = 235,146) and ResNet-18, 8 peers
     python benchmarks/bench_robust_agg.py --models mlp --repeats 30
     python benchmarks/bench_robust_agg.py --aggregators geometric_median,krum
+    python benchmarks/bench_robust_agg.py --aggregators bulyan
 
 For each model and aggregator the same 8 co-located peers are aggregated two ways, alternating in
 one process on identical inputs (the rows are restored, untimed, before every call):
 
-* device : ``weights_plane.aggregate_krum`` / ``aggregate_trimmed_mean`` / ``aggregate_geometric_median`` (the kernels of
+* device : ``weights_plane.aggregate_krum`` / ``aggregate_trimmed_mean`` / ``aggregate_geometric_median`` / ``aggregate_bulyan`` (the kernels of
   ``csrc/kernels/fl_ops.hip`` on the live rows), host clock around the call plus a device
   synchronise;
 * generic: what ``join_aggregation`` does for an aggregator without a device path — a wire model
@@ -19,7 +20,9 @@ calls, and their achieved GB/s computed from the bytes the algorithm needs (K ro
 reads the chosen rows and writes P rows). The geometric median's distance/reweight pair is the
 difference of a 5-step and a 1-step call, divided by 4: allocation and call overhead cancel; the
 whole 1-step call (screen + one step: two pairs) is reported next to Krum's distance/select pair,
-which is timed in the same process for that. One JSON line per (model, aggregator). Needs a GPU:
+which is timed in the same process for that. Bulyan's ``k_bulyan_mean<K, f>`` is timed alone from a
+selection made before the window, next to ``k_trimmed_mean<K>`` on the same rows in the same
+process. One JSON line per (model, aggregator). Needs a GPU:
 ``--device cpu`` only rehearses the plumbing and its timings mean nothing.
 """
 
@@ -42,7 +45,7 @@ FLIPPED = 5
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--models", default="mlp,resnet18")
-    ap.add_argument("--aggregators", default="krum,trimmed_mean,geometric_median")
+    ap.add_argument("--aggregators", default="krum,trimmed_mean,geometric_median,bulyan")
     ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"])
     ap.add_argument("--repeats", type=int, default=20, help="timed device calls per case (generic: --generic-repeats)")
     ap.add_argument("--generic-repeats", type=int, default=5)
@@ -100,12 +103,12 @@ def run_case(model_name: str, agg_name: str, args) -> dict:
     import torch
 
     from myfyp_amd import ops
-    from myfyp_amd.learning.aggregators import GeometricMedian, Krum, TrimmedMean
+    from myfyp_amd.learning.aggregators import Bulyan, GeometricMedian, Krum, TrimmedMean
     from myfyp_amd.parallel import weights_plane
     from myfyp_amd.parallel.federation import Federation
 
     make = {"krum": lambda: Krum(num_byzantine=1, multi=3), "trimmed_mean": lambda: TrimmedMean(beta=0.125),
-            "geometric_median": lambda: GeometricMedian(iters=3)}[agg_name]
+            "geometric_median": lambda: GeometricMedian(iters=3), "bulyan": lambda: Bulyan(num_byzantine=1)}[agg_name]
     Federation.reset()
     fed = Federation.init()
     nodes = build_nodes(model_name, make)
@@ -121,7 +124,7 @@ def run_case(model_name: str, agg_name: str, args) -> dict:
         rows0 = torch.stack([(-base if i == FLIPPED else base + 1e-3 * (1 + 0.15 * i) * 0.05 * torch.randn(n, generator=g)) for i in range(PEERS)]).to(dev)
         agg = nodes[0].aggregator
         device_fn = {"krum": weights_plane.aggregate_krum, "trimmed_mean": weights_plane.aggregate_trimmed_mean,
-                     "geometric_median": weights_plane.aggregate_geometric_median}[agg_name]
+                     "geometric_median": weights_plane.aggregate_geometric_median, "bulyan": weights_plane.aggregate_bulyan}[agg_name]
 
         def restore() -> None:
             with torch.no_grad():
@@ -196,6 +199,20 @@ def run_case(model_name: str, agg_name: str, args) -> dict:
                                                                                "bytes": "K rows read"}
             kernels["coef_mean"] = {"ms": round(ms_mean, 4), "GBps": round(2 * PEERS * n * 4 / ms_mean / 1e6, 1), "bytes": "K rows read, P rows written",
                                     "note": "difference of the two windows"}
+        elif agg_name == "bulyan":
+            scratch = [torch.empty(n, dtype=torch.float32, device=dev) for _ in range(PEERS)]
+            coef = ops.bulyan_into(flats, [], 1)[2]
+            ms_sel = event_ms(dev, lambda: ops.bulyan_into(flats, [], 1), it, wu)
+            ms_mean = event_ms(dev, lambda: ops.bulyan_mean_into(flats, scratch, coef, 1), it, wu)
+            ms_trim = event_ms(dev, lambda: ops.trimmed_mean_into(flats, scratch, 1), it, wu)
+            ms_all = event_ms(dev, lambda: ops.bulyan_into(flats, scratch, 1), it, wu)
+            picked = PEERS - 2
+            kernels["pairwise_sqdist+bulyan_select"] = {"ms": round(ms_sel, 4), "GBps": round(PEERS * n * 4 / ms_sel / 1e6, 1), "bytes": "K rows read"}
+            kernels["bulyan_mean"] = {"ms": round(ms_mean, 4), "GBps": round((picked + PEERS) * n * 4 / ms_mean / 1e6, 1),
+                                      "bytes": "K - 2f picked rows read, P rows written"}
+            kernels["trimmed_mean (same rows, same process)"] = {"ms": round(ms_trim, 4), "GBps": round(2 * PEERS * n * 4 / ms_trim / 1e6, 1),
+                                                                 "bytes": "K rows read, P rows written"}
+            kernels["whole call (3 launches)"] = {"ms": round(ms_all, 4)}
         else:
             scratch = [torch.empty(n, dtype=torch.float32, device=dev) for _ in range(PEERS)]
             ms = event_ms(dev, lambda: ops.trimmed_mean_into(flats, scratch, 1), it, wu)

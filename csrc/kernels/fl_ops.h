@@ -59,6 +59,16 @@ void fl_coef_mean(const OutPtrs& outs, int P, const RowPtrs& rows, int K, const 
 inline int64_t fl_geomed_work(int64_t n, int K) { return (int64_t)fl_krum_grid(n, K) * K + 16; }
 void fl_geometric_median(float* work, const RowPtrs& rows, const RowW& w, int K, int iters, double nu, int64_t n, float* coef, double* dist,
                          double* obj, hipStream_t s);
+// Bulyan (El Mhamdi, Guerraoui, Rouault, 2018) of rows 0..K-1 with at most f attackers (K >= 4f + 3,
+// or f == 0): the distances of fl_krum_select on the same grid (work holds the same floats), theta =
+// K - 2f rows picked by iterated Krum, then per coordinate the mean of the K - 4f picked values
+// closest to their median into out rows 0..P-1 (outputs may alias rows; P == 0: selection only).
+// Device outputs dist[K*K], score[K] (double: Krum's for the same f), pick[K] (int: the iteration a
+// row was picked at, or -1) and coef[K] (float: 1/theta for a picked row, else 0). Three launches.
+void fl_bulyan(float* work, const OutPtrs& outs, int P, const RowPtrs& rows, int K, int f, int64_t n, double* dist, double* score, int* pick,
+               float* coef, hipStream_t s);
+// The last of fl_bulyan's launches alone: coef[K] in device memory marks the K - 2f picked rows.
+void fl_bulyan_mean(const OutPtrs& outs, int P, const RowPtrs& rows, int K, int f, const float* coef, int64_t n, hipStream_t s);
 // SCAFFOLD server step, packed buffer [Σ w_k dy_k | Σ w_k | Σ dc_k | K] (2n + 2 floats):
 //   reduce: buf <- the local contributions (before the cross-rank all-reduce)
 //   apply : out rows <- x_start + glr · buf[0:n] / buf[n];  c <- (c_init ? 0 : c) + buf[n+1:2n+1] / buf[2n+1]

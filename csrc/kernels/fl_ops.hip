@@ -433,12 +433,9 @@ __global__ __launch_bounds__(FL_BLOCK) void k_pairwise_sqdist(float* __restrict_
 // max(1, min(m, K)) lowest scores are chosen, the lower index winning a tie; a NaN (a peer that
 // sent one) orders last, as numpy's sort does. coef[i] = w_i / Σ_chosen w, 0 for the others.
 #define KRUM_SELECT_BLOCK 1024
-__global__ __launch_bounds__(KRUM_SELECT_BLOCK) void k_krum_select(const float* __restrict__ work, int G, int K, int f, int m, RowW w,
-                                                                   double* __restrict__ dist, double* __restrict__ score, float* __restrict__ coef) {
-  __shared__ double d[16][16];
-  __shared__ double sc[16];
-  __shared__ int chosen[16];
-  __shared__ double part[KRUM_SELECT_BLOCK];
+// The slab sum of the one-block selection kernels (Krum, Bulyan): d[i][j] <- pair (i, j)'s sum in
+// the order above, 0 on the diagonal. Ends with a barrier; every thread of the block calls it.
+__device__ __forceinline__ void krum_sum_slabs(const float* __restrict__ work, int G, int K, double (*d)[16], double* part) {
   const int t = threadIdx.x;
   const int NP = K * (K - 1) / 2;
   if (t < 256) (&d[0][0])[t] = 0.0;
@@ -473,27 +470,43 @@ __global__ __launch_bounds__(KRUM_SELECT_BLOCK) void k_krum_select(const float* 
     d[j][i] = s;
   }
   __syncthreads();
+}
+
+// Row t's score: its cnt smallest distances to the rows whose bit in taken is clear, summed in
+// ascending order (the lower index first among equals, a NaN as +inf).
+__device__ __forceinline__ double krum_row_score(double (*d)[16], int t, int K, int cnt, unsigned taken) {
+  double s = 0.0;
+  for (int c = 0; c < cnt; ++c) {
+    int best = -1;
+    double bk = 0.0;
+    for (int j = 0; j < K; ++j) {
+      if ((taken >> j) & 1u) continue;
+      const double key = d[t][j] != d[t][j] ? __builtin_huge_val() : d[t][j];
+      if (best < 0 || key < bk) {
+        best = j;
+        bk = key;
+      }
+    }
+    taken |= 1u << best;
+    s += d[t][best];
+  }
+  return s;
+}
+
+__global__ __launch_bounds__(KRUM_SELECT_BLOCK) void k_krum_select(const float* __restrict__ work, int G, int K, int f, int m, RowW w,
+                                                                   double* __restrict__ dist, double* __restrict__ score, float* __restrict__ coef) {
+  __shared__ double d[16][16];
+  __shared__ double sc[16];
+  __shared__ int chosen[16];
+  __shared__ double part[KRUM_SELECT_BLOCK];
+  const int t = threadIdx.x;
+  krum_sum_slabs(work, G, K, d, part);
   for (int q = t; q < K * K; q += KRUM_SELECT_BLOCK) dist[q] = d[q / K][q % K];
   if (t < K) {
     int cnt = K - f - 2;
     if (cnt < 1) cnt = 1;
     if (cnt > K - 1) cnt = K - 1;
-    unsigned taken = 1u << t;
-    double s = 0.0;
-    for (int c = 0; c < cnt; ++c) {
-      int best = -1;
-      double bk = 0.0;
-      for (int j = 0; j < K; ++j) {
-        if ((taken >> j) & 1u) continue;
-        const double key = d[t][j] != d[t][j] ? __builtin_huge_val() : d[t][j];
-        if (best < 0 || key < bk) {
-          best = j;
-          bk = key;
-        }
-      }
-      taken |= 1u << best;
-      s += d[t][best];
-    }
+    const double s = krum_row_score(d, t, K, cnt, 1u << t);
     sc[t] = s;
     score[t] = s;
   }
@@ -545,6 +558,142 @@ __global__ __launch_bounds__(FL_BLOCK) void k_coef_mean(OutPtrs outs, int P, Row
       acc.x = fmaf(c[k], v.x, acc.x); acc.y = fmaf(c[k], v.y, acc.y); acc.z = fmaf(c[k], v.z, acc.z); acc.w = fmaf(c[k], v.w, acc.w);
     }
     for (int p = 0; p < P; ++p) store4<VEC>(outs.p[p], g, n, acc);
+  }
+}
+
+// Bulyan (El Mhamdi, Guerraoui, Rouault, 2018) in three launches: k_pairwise_sqdist<K> on Krum's
+// grid, then
+//   k_bulyan_select    : one block sums the slabs as k_krum_select does and picks θ = K − 2f rows by
+//                        iterated Krum; writes dist / score / pick / coef (1/θ for a picked row)
+//   k_bulyan_mean<K, F>: per coordinate over the picked rows, the mean of the β = K − 4f values
+//                        closest to their median
+// Iteration it of the selection: every remaining row's score over its clamp(r − f − 2, 1, r − 1)
+// nearest remaining rows (r rows remain), the lowest score picked, the lower index winning a tie,
+// a NaN ordering as +inf. score[] is the first iteration's: Krum's score for the same f.
+__global__ __launch_bounds__(KRUM_SELECT_BLOCK) void k_bulyan_select(const float* __restrict__ work, int G, int K, int f, double* __restrict__ dist,
+                                                                     double* __restrict__ score, int* __restrict__ pick, float* __restrict__ coef) {
+  __shared__ double d[16][16];
+  __shared__ double sc[16];
+  __shared__ int picked[16];
+  __shared__ unsigned remaining;
+  __shared__ double part[KRUM_SELECT_BLOCK];
+  const int t = threadIdx.x;
+  krum_sum_slabs(work, G, K, d, part);
+  for (int q = t; q < K * K; q += KRUM_SELECT_BLOCK) dist[q] = d[q / K][q % K];
+  const int theta = K - 2 * f;
+  if (t < K) picked[t] = -1;
+  if (t == 0) remaining = (1u << K) - 1u;
+  __syncthreads();
+  for (int it = 0; it < theta; ++it) {
+    const unsigned R = remaining;
+    const int r = K - it;
+    int cnt = r - f - 2;
+    if (cnt < 1) cnt = 1;
+    if (cnt > r - 1) cnt = r - 1;  // r == 1: no distance, the remaining row is picked
+    if (t < K && ((R >> t) & 1u)) {
+      const double s = krum_row_score(d, t, K, cnt, ~R | (1u << t));
+      sc[t] = s;
+      if (it == 0) score[t] = s;
+    }
+    __syncthreads();
+    if (t == 0) {
+      int best = -1;
+      double bk = 0.0;
+      for (int j = 0; j < K; ++j) {
+        if (!((R >> j) & 1u)) continue;
+        const double key = sc[j] != sc[j] ? __builtin_huge_val() : sc[j];
+        if (best < 0 || key < bk) {
+          best = j;
+          bk = key;
+        }
+      }
+      picked[best] = it;
+      remaining = R & ~(1u << best);
+    }
+    __syncthreads();
+  }
+  if (t < K) {
+    pick[t] = picked[t];
+    coef[t] = picked[t] >= 0 ? 1.f / (float)theta : 0.f;
+  }
+}
+
+// Stage 2 on one coordinate: v[0 .. θ) ascending (the picked rows' values; the slots behind them
+// hold +inf). m their median; among the window starts s in [0, 2F] the one that minimises
+// max(m − v[s], v[s+β−1] − m), the lowest s winning a tie; the window summed in ascending order and
+// divided by β, all in fp32. K and F are template parameters: every index is static.
+template <int K, int F>
+__device__ __forceinline__ float bulyan_window_mean(const float (&v)[K]) {
+  constexpr int TH = K - 2 * F, B = K - 4 * F;
+  static_assert(B >= 1, "Bulyan needs K > 4f");
+  const float m = (TH & 1) ? v[(TH - 1) / 2] : 0.5f * (v[TH / 2 - 1] + v[TH / 2]);
+  float best = fmaxf(m - v[0], v[B - 1] - m);
+  float sum = v[0];
+#pragma unroll
+  for (int k = 1; k < B; ++k) sum += v[k];
+#pragma unroll
+  for (int s = 1; s <= 2 * F; ++s) {
+    const float cost = fmaxf(m - v[s], v[s + B - 1] - m);
+    float ws = v[s];
+#pragma unroll
+    for (int k = 1; k < B; ++k) ws += v[s + k];
+    if (cost < best) {
+      best = cost;
+      sum = ws;
+    }
+  }
+  return sum / (float)B;
+}
+
+// Rows of coefficient 0 are never read: their slots hold +inf, so the compare-exchange network (the
+// median's) leaves the θ picked values in front. Every thread loads its four coordinates from all
+// picked rows before it stores: outputs may alias rows.
+template <int K, int F, bool VEC>
+__global__ __launch_bounds__(FL_BLOCK) void k_bulyan_mean(OutPtrs outs, int P, RowPtrs rows, const float* __restrict__ coef, int64_t n) {
+  bool on[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) on[k] = coef[k] != 0.f;
+  const float inf = __builtin_huge_valf();
+  const int64_t groups = (n + 3) / 4;
+  const int64_t stride = (int64_t)gridDim.x * FL_BLOCK;
+  for (int64_t g = (int64_t)blockIdx.x * FL_BLOCK + threadIdx.x; g < groups; g += stride) {
+    float4 x[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) x[k] = {inf, inf, inf, inf};
+    // one decision for all K rows (see k_gm_dist); on[k] is uniform over the grid
+    if (VEC && 4 * g + 4 <= n) {
+#pragma unroll
+      for (int k = 0; k < K; ++k)
+        if (on[k]) x[k] = reinterpret_cast<const float4*>(rows.p[k])[g];
+    } else {
+#pragma unroll
+      for (int k = 0; k < K; ++k)
+        if (on[k]) x[k] = load4<false>(rows.p[k], g, n);
+    }
+    float v[4][K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      v[0][k] = x[k].x;
+      v[1][k] = x[k].y;
+      v[2][k] = x[k].z;
+      v[3][k] = x[k].w;
+    }
+    float o[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+#pragma unroll
+      for (int a = 0; a < K; ++a) {
+#pragma unroll
+        for (int b = 0; b < K - 1 - a; ++b) {
+          const float lo = fminf(v[c][b], v[c][b + 1]);
+          v[c][b + 1] = fmaxf(v[c][b], v[c][b + 1]);
+          v[c][b] = lo;
+        }
+      }
+      o[c] = bulyan_window_mean<K, F>(v[c]);
+    }
+    const float4 res = {o[0], o[1], o[2], o[3]};
+    for (int p = 0; p < P; ++p) store4<VEC>(outs.p[p], g, n, res);
   }
 }
 
@@ -824,8 +973,8 @@ static bool all_aligned16(const RowPtrs& rows, int K, const OutPtrs* outs, int P
   for (int p = 0; outs != nullptr && p < P; ++p) bits |= reinterpret_cast<uintptr_t>(outs->p[p]);
   return (bits & 15u) == 0;
 }
-void fl_krum_select(float* work, const RowPtrs& rows, const RowW& w, int K, int f, int m, int64_t n, double* dist, double* score, float* coef,
-                    hipStream_t s) {
+// k_pairwise_sqdist<K> on fl_krum_grid(n, K) blocks; returns the grid (0 for K == 1: no pair)
+static unsigned launch_pairwise_sqdist(float* work, const RowPtrs& rows, int K, int64_t n, hipStream_t s) {
   const unsigned grid = K > 1 ? fl_krum_grid(n, K) : 0;
   const bool vec = all_aligned16(rows, K, nullptr, 0);
   const dim3 g(grid), b(FL_BLOCK);
@@ -840,6 +989,11 @@ void fl_krum_select(float* work, const RowPtrs& rows, const RowW& w, int K, int 
 #undef DIST_CASE
     default: break;  // K == 1: no pair, nothing to measure
   }
+  return grid;
+}
+void fl_krum_select(float* work, const RowPtrs& rows, const RowW& w, int K, int f, int m, int64_t n, double* dist, double* score, float* coef,
+                    hipStream_t s) {
+  const unsigned grid = launch_pairwise_sqdist(work, rows, K, n, s);
   hipLaunchKernelGGL(k_krum_select, dim3(1), dim3(KRUM_SELECT_BLOCK), 0, s, work, (int)grid, K, f, m, w, dist, score, coef);
 }
 void fl_coef_mean(const OutPtrs& outs, int P, const RowPtrs& rows, int K, const float* coef, int64_t n, hipStream_t s) {
@@ -856,6 +1010,40 @@ void fl_coef_mean(const OutPtrs& outs, int P, const RowPtrs& rows, int K, const 
 #undef COEF_CASE
     default: break;
   }
+}
+// k_bulyan_mean<K, F>: F runs over the attacker bounds K admits (K >= 4F + 3, or F == 0)
+template <int K, int F>
+static void bulyan_mean_launch(bool vec, dim3 g, const OutPtrs& outs, int P, const RowPtrs& rows, const float* coef, int64_t n, hipStream_t s) {
+  if (vec) hipLaunchKernelGGL((k_bulyan_mean<K, F, true>), g, dim3(FL_BLOCK), 0, s, outs, P, rows, coef, n);
+  else hipLaunchKernelGGL((k_bulyan_mean<K, F, false>), g, dim3(FL_BLOCK), 0, s, outs, P, rows, coef, n);
+}
+template <int K>
+static void bulyan_mean_f(int f, bool vec, dim3 g, const OutPtrs& outs, int P, const RowPtrs& rows, const float* coef, int64_t n, hipStream_t s) {
+  if (f == 0) bulyan_mean_launch<K, 0>(vec, g, outs, P, rows, coef, n, s);
+  if constexpr (K >= 7)
+    if (f == 1) bulyan_mean_launch<K, 1>(vec, g, outs, P, rows, coef, n, s);
+  if constexpr (K >= 11)
+    if (f == 2) bulyan_mean_launch<K, 2>(vec, g, outs, P, rows, coef, n, s);
+  if constexpr (K >= 15)
+    if (f == 3) bulyan_mean_launch<K, 3>(vec, g, outs, P, rows, coef, n, s);
+}
+void fl_bulyan_mean(const OutPtrs& outs, int P, const RowPtrs& rows, int K, int f, const float* coef, int64_t n, hipStream_t s) {
+  const bool vec = all_aligned16(rows, K, &outs, P);
+  const dim3 g(grid_for((n + 3) / 4));
+  switch (K) {
+#define BUL_CASE(KK) \
+  case KK: bulyan_mean_f<KK>(f, vec, g, outs, P, rows, coef, n, s); break;
+    BUL_CASE(1) BUL_CASE(2) BUL_CASE(3) BUL_CASE(4) BUL_CASE(5) BUL_CASE(6) BUL_CASE(7) BUL_CASE(8)
+    BUL_CASE(9) BUL_CASE(10) BUL_CASE(11) BUL_CASE(12) BUL_CASE(13) BUL_CASE(14) BUL_CASE(15) BUL_CASE(16)
+#undef BUL_CASE
+    default: break;
+  }
+}
+void fl_bulyan(float* work, const OutPtrs& outs, int P, const RowPtrs& rows, int K, int f, int64_t n, double* dist, double* score, int* pick,
+               float* coef, hipStream_t s) {
+  const unsigned grid = launch_pairwise_sqdist(work, rows, K, n, s);
+  hipLaunchKernelGGL(k_bulyan_select, dim3(1), dim3(KRUM_SELECT_BLOCK), 0, s, work, (int)grid, K, f, dist, score, pick, coef);
+  if (P > 0) fl_bulyan_mean(outs, P, rows, K, f, coef, n, s);
 }
 void fl_geometric_median(float* work, const RowPtrs& rows, const RowW& w, int K, int iters, double nu, int64_t n, float* coef, double* dist,
                          double* obj, hipStream_t s) {
@@ -903,14 +1091,16 @@ void fl_scale_add_noise(float* t, int64_t n, float scale, float sigma, uint64_t 
 extern "C" int myfyp_warm_fl_ops() {
   hipFuncAttributes attr;
   // the robust aggregators' launches of the headline peer count (8) resolve here too, so a first
-  // Krum / trimmed-mean / geometric-median round pays no lookup behind a running epoch
+  // Krum / trimmed-mean / geometric-median / Bulyan round pays no lookup behind a running epoch
   const void* fns[] = {reinterpret_cast<const void*>(&k_weighted_sum),
                        reinterpret_cast<const void*>(&k_trimmed_mean<8>),
                        reinterpret_cast<const void*>(&k_pairwise_sqdist<8, true>),
                        reinterpret_cast<const void*>(&k_krum_select),
                        reinterpret_cast<const void*>(&k_coef_mean<8, true>),
                        reinterpret_cast<const void*>(&k_gm_dist<8, true>),
-                       reinterpret_cast<const void*>(&k_gm_reweight)};
+                       reinterpret_cast<const void*>(&k_gm_reweight),
+                       reinterpret_cast<const void*>(&k_bulyan_select),
+                       reinterpret_cast<const void*>(&k_bulyan_mean<8, 1, true>)};
   for (const void* fn : fns)
     if (hipFuncGetAttributes(&attr, fn) != hipSuccess) return 1;
   return 0;

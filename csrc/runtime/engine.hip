@@ -1038,6 +1038,53 @@ int myfyp_krum_multi(const uint64_t* outs, int P, const uint64_t* srcs, const fl
   }
   return 0;
 }
+static bool bulyan_ok(int K, int P, int f, int64_t n) {
+  if (!rows_ok(K, "bulyan") || (P != 0 && !rows_ok(P, "bulyan outputs"))) return false;
+  if (f < 0 || (f > 0 && K < 4 * f + 3)) {
+    g_last_error = "bulyan: f >= 0 and K >= 4f + 3 (got K = " + std::to_string(K) + ", f = " + std::to_string(f) + ")";
+    return false;
+  }
+  if (n < 1) {
+    g_last_error = "bulyan: n >= 1";
+    return false;
+  }
+  return true;
+}
+// Bulyan with at most f attackers among the K rows (device outputs dist[K*K], score[K]: double;
+// pick[K]: int; coef[K]: float), then, with P > 0, out rows <- per coordinate the mean of the K - 4f
+// picked values closest to their median. work: myfyp_krum_grid(n, K) * K(K-1)/2 floats. Enqueues only.
+int myfyp_bulyan_multi(const uint64_t* outs, int P, const uint64_t* srcs, int K, int f, int64_t n, float* work, double* dist, double* score, int* pick,
+                       float* coef, void* stream) {
+  if (!bulyan_ok(K, P, f, n)) return 2;
+  if (srcs == nullptr || (P > 0 && outs == nullptr) || dist == nullptr || score == nullptr || pick == nullptr || coef == nullptr ||
+      (K > 1 && work == nullptr)) {
+    g_last_error = "bulyan: the row tables and the work / dist / score / pick / coef buffers are required";
+    return 2;
+  }
+  RowPtrs rows{};
+  OutPtrs o{};
+  for (int k = 0; k < K; ++k) rows.p[k] = reinterpret_cast<const float*>(srcs[k]);
+  for (int p = 0; p < P; ++p) o.p[p] = reinterpret_cast<float*>(outs[p]);
+  fl_bulyan(work, o, P, rows, K, f, n, dist, score, pick, coef, (hipStream_t)stream);
+  CHECK_HIP(hipGetLastError());
+  return 0;
+}
+// The last launch of myfyp_bulyan_multi alone, from a selection already made: coef[K] (device)
+// is != 0 for exactly K - 2f rows; the others are never read.
+int myfyp_bulyan_mean_multi(const uint64_t* outs, int P, const uint64_t* srcs, int K, int f, int64_t n, const float* coef, void* stream) {
+  if (!bulyan_ok(K, P, f, n)) return 2;
+  if (P < 1 || srcs == nullptr || outs == nullptr || coef == nullptr) {
+    g_last_error = "bulyan_mean: at least one output, the row tables and coef are required";
+    return 2;
+  }
+  RowPtrs rows{};
+  OutPtrs o{};
+  for (int k = 0; k < K; ++k) rows.p[k] = reinterpret_cast<const float*>(srcs[k]);
+  for (int p = 0; p < P; ++p) o.p[p] = reinterpret_cast<float*>(outs[p]);
+  fl_bulyan_mean(o, P, rows, K, f, coef, n, (hipStream_t)stream);
+  CHECK_HIP(hipGetLastError());
+  return 0;
+}
 // Floats of the workspace of myfyp_geomed_multi for n coordinates of K rows.
 int64_t myfyp_geomed_work(int64_t n, int K) { return fl_geomed_work(n, K); }
 // Geometric median (smoothed Weiszfeld, iters steps; device outputs coef[K]: float, dist[K] and

@@ -13,7 +13,8 @@ plane which reduction implements it (``"mean"`` → one weighted all-reduce, ``"
 topology mixing, ``"scaffold"`` → packed all-reduce + apply, ``"median"`` / ``"trimmed_mean"`` →
 all-gather + per-coordinate sorting-network kernel, ``"krum"`` → all-gather + distance, selection
 and weighted-mean kernels, ``"geometric_median"`` → all-gather + distance, reweighting and
-weighted-mean kernels, ``None`` → host fallback over gathered wire models).
+weighted-mean kernels, ``"bulyan"`` → all-gather + distance, iterated-selection and
+closest-to-the-median kernels, ``None`` → host fallback over gathered wire models).
 """
 
 from __future__ import annotations

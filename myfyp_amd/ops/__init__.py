@@ -16,6 +16,9 @@ Ops
 * ``geometric_median_into`` — geometric median (RFA, smoothed Weiszfeld): a screen of non-finite
   rows, then per step the distances to the current point and the reweighting, all on the device
   (K ≤ 16); returns ``(coef, dist, objective)``
+* ``bulyan_into`` — Bulyan: Krum's distances, θ = K − 2f rows picked by iterated Krum, then per
+  coordinate the mean of the K − 4f picked values closest to their median, all on the device
+  (K ≤ 16); returns ``(dist, score, coef, pick)``
 * ``adam_step`` / ``sgd_step`` — fused optimizers over a flat buffer, optionally with the FedProx
   proximal term and the SCAFFOLD control-variate correction fused in (K5, K8, K13)
 * ``scale_add_noise`` — attack injection (sign flip / Gaussian noise, K14)
@@ -38,6 +41,7 @@ __all__ = [
     "trimmed_mean_into",
     "krum_into",
     "geometric_median_into",
+    "bulyan_into",
     "adam_step",
     "sgd_step",
     "scale_add_noise",
@@ -253,6 +257,138 @@ def krum_into(rows: Sequence[torch.Tensor], outs: Sequence[torch.Tensor], weight
         for o in outs:
             o.copy_(mean)
     return dist, score, coef
+
+
+def bulyan_check(k: int, f: int) -> int:
+    """The attacker bound of a Bulyan call, checked: ``f >= 0`` and ``K >= 4f + 3``. With ``f == 0``
+    nothing is rejected or trimmed (the result is the mean of all rows), so any ``K >= 1`` does."""
+    if int(f) != f or f < 0:
+        raise ValueError(f"Bulyan: the attacker bound f must be an integer >= 0, got f = {f} (K = {k})")
+    f = int(f)
+    if k < 1 or (f > 0 and k < 4 * f + 3):
+        raise ValueError(f"Bulyan needs K >= 4f + 3 models: K = {k}, f = {f} needs {4 * f + 3}")
+    return f
+
+
+def bulyan_select(dist, f: int):
+    """Bulyan's stage 1 on a K x K table of squared distances (anything ``float()`` reads): θ = K − 2f
+    rounds, each scoring every remaining row by the sum, in ascending order, of its
+    ``clamp(r − f − 2, 1, r − 1)`` smallest distances to the other remaining rows (r of them remain; a
+    NaN orders as +inf) and picking the lowest score, the lower index winning a tie. Returns
+    ``(pick, score)``: the round each row was picked at (−1: never) and the first round's scores."""
+    k = len(dist)
+    inf = float("inf")
+    d = [[float(dist[i][j]) for j in range(k)] for i in range(k)]
+    remaining = list(range(k))
+    pick = [-1] * k
+    first = [0.0] * k
+    for it in range(k - 2 * f):
+        r = len(remaining)
+        cnt = min(max(r - f - 2, 1), r - 1)
+        scores = {}
+        for i in remaining:
+            others = [d[i][j] for j in remaining if j != i]
+            others.sort(key=lambda v: inf if v != v else v)  # stable; NaN last
+            scores[i] = float(sum(others[:cnt]))
+        if it == 0:
+            first = [scores[i] for i in range(k)]
+        best = min(remaining, key=lambda i: (inf if scores[i] != scores[i] else scores[i], i))
+        pick[best] = it
+        remaining.remove(best)
+    return pick, first
+
+
+def _bulyan_stage2(picked: Sequence[torch.Tensor], outs: Sequence[torch.Tensor], k: int, f: int) -> None:
+    """Stage 2 of :func:`bulyan_into` over the θ picked rows, in fp32 torch math."""
+    theta, beta = k - 2 * f, k - 4 * f
+    v, _ = torch.sort(torch.stack([r.float().reshape(-1) for r in picked]), dim=0)
+    m = v[(theta - 1) // 2] if theta % 2 else 0.5 * (v[theta // 2 - 1] + v[theta // 2])
+    best, mean = None, None
+    for s in range(2 * f + 1):
+        cost = torch.maximum(m - v[s], v[s + beta - 1] - m)
+        acc = v[s].clone()
+        for j in range(1, beta):
+            acc += v[s + j]
+        if best is None:
+            best, mean = cost, acc
+        else:
+            better = cost < best
+            best = torch.where(better, cost, best)
+            mean = torch.where(better, acc, mean)
+    mean = mean / torch.tensor(float(beta), dtype=torch.float32, device=mean.device)
+    for o in outs:
+        o.copy_(mean)
+
+
+def bulyan_mean_into(rows: Sequence[torch.Tensor], outs: Sequence[torch.Tensor], coef: torch.Tensor, f: int) -> None:
+    """Stage 2 of :func:`bulyan_into` alone, from a selection already made: ``coef [K]`` is != 0
+    for exactly the K − 2f picked rows, and the others are never read. On the GPU one launch
+    (``k_bulyan_mean<K, f>``) that takes ``coef`` from device memory."""
+    k = len(rows)
+    f = bulyan_check(k, f)
+    if not outs:
+        return
+    if _native_rows(rows, outs) and coef.device == rows[0].device and coef.dtype == torch.float32 and coef.is_contiguous() and coef.numel() == k:
+        src, keep_s = _host_ptrs(rows)
+        dst, keep_d = _host_ptrs(outs)
+        _native.check(_lib().myfyp_bulyan_mean_multi(dst, len(outs), src, k, f, rows[0].numel(), coef.data_ptr(), _stream()), "bulyan_mean_multi")
+        return
+    on = coef.tolist()
+    if sum(1 for c in on if c != 0) != k - 2 * f:
+        raise ValueError(f"Bulyan: coef must mark K - 2f = {k - 2 * f} rows, got {sum(1 for c in on if c != 0)}")
+    _bulyan_stage2([rows[i] for i in range(k) if on[i] != 0], outs, k, f)
+
+
+def bulyan_into(rows: Sequence[torch.Tensor], outs: Sequence[torch.Tensor], f: int):
+    """Bulyan (El Mhamdi, Guerraoui, Rouault, 2018) over 1-D fp32 rows with at most ``f`` attackers
+    (``K >= 4f + 3``; ``f == 0`` takes any K). Sample weights are not used.
+
+    Stage 1: squared distances from differences (Krum's), then θ = K − 2f rows picked by iterated
+    Krum (:func:`bulyan_select`). Stage 2, per coordinate over the picked rows only, in fp32: the
+    values sorted, ``m`` their median (the mean of the middle two for an even θ), the window of
+    β = K − 4f consecutive values starting at ``s`` in ``[0, 2f]`` that minimises
+    ``max(m − v[s], v[s+β−1] − m)`` (the lowest ``s`` wins a tie): the β values closest to the
+    median; ``outs[p]`` = their sum, taken in ascending order, divided by β. With at most f
+    non-finite rows those are never picked. The row order matters only through exact ties, which
+    are common in the last rounds: a score over one nearest row is the same for the two closest
+    rows left. Returns ``(dist [K, K] float64, score [K] float64: Krum's
+    score for the same f, coef [K] float32: 1/θ for a picked row and 0 otherwise, pick [K] int32: the
+    round a row was picked at, −1 otherwise)`` on the rows' device; ``outs=[]`` gives the selection only.
+
+    On the GPU (K <= 16 rows, <= 16 outputs, which may alias the rows) it is three launches —
+    ``k_pairwise_sqdist<K>``, ``k_bulyan_select``, ``k_bulyan_mean<K, f>`` — that only enqueue.
+    Elsewhere: torch math, the distances in float64 (the oracle)."""
+    k = len(rows)
+    f = bulyan_check(k, f)
+    dev = rows[0].device
+    n = rows[0].numel()
+    if n < 1 or any(t.numel() != n for t in [*rows, *outs]):
+        raise ValueError(f"Bulyan: rows and outputs must share one length >= 1, got {[t.numel() for t in [*rows, *outs]]}")
+    if _native_rows(rows, outs):
+        lib = _lib()
+        work = torch.empty(max(1, int(lib.myfyp_krum_grid(n, k)) * (k * (k - 1) // 2)), dtype=torch.float32, device=dev)
+        dist = torch.empty(k, k, dtype=torch.float64, device=dev)
+        score = torch.empty(k, dtype=torch.float64, device=dev)
+        coef = torch.empty(k, dtype=torch.float32, device=dev)
+        pick = torch.empty(k, dtype=torch.int32, device=dev)
+        src, keep_s = _host_ptrs(rows)
+        dst, keep_d = _host_ptrs(outs)
+        _native.check(lib.myfyp_bulyan_multi(dst, len(outs), src, k, f, n, work.data_ptr(), dist.data_ptr(), score.data_ptr(), pick.data_ptr(),
+                                             coef.data_ptr(), _stream()), "bulyan_multi")
+        return dist, score, coef, pick
+    x = [r.double().reshape(-1) for r in rows]
+    dist = torch.zeros(k, k, dtype=torch.float64)
+    for i in range(k):
+        for j in range(i + 1, k):
+            dist[i, j] = dist[j, i] = float((x[i] - x[j]).square().sum())
+    picks, first = bulyan_select(dist.tolist(), f)
+    theta, beta = k - 2 * f, k - 4 * f
+    pick = torch.tensor(picks, dtype=torch.int32)
+    coef = torch.where(pick >= 0, torch.tensor(1.0, dtype=torch.float32) / torch.tensor(float(theta), dtype=torch.float32), torch.zeros((), dtype=torch.float32))
+    score = torch.tensor(first, dtype=torch.float64)
+    if outs:
+        _bulyan_stage2([rows[i] for i in range(k) if picks[i] >= 0], outs, k, f)
+    return dist.to(dev), score.to(dev), coef.to(dev), pick.to(dev)
 
 
 GEOMED_MAX_ITERS = 32

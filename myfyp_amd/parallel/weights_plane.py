@@ -730,7 +730,7 @@ def _mesh_neighbors(fed: Federation, peers, index, w, local, learners) -> None:
 
 
 # aggregator kinds reduced on the device (no wire models, no host copies)
-DEVICE_KINDS = ("mean", "neighbor", "scaffold", "median", "krum", "trimmed_mean", "geometric_median")
+DEVICE_KINDS = ("mean", "neighbor", "scaffold", "median", "krum", "trimmed_mean", "geometric_median", "bulyan")
 
 
 def _scaffold_cb(learner):
@@ -938,9 +938,9 @@ def _median(fed: Federation, arrived: Dict[str, Tuple[float, Any]]) -> None:
 
 
 # ---------------------------------------------------------------------------------------------
-# robust aggregation: coordinate-wise trimmed mean, (Multi-)Krum and the geometric median
+# robust aggregation: coordinate-wise trimmed mean, (Multi-)Krum, the geometric median and Bulyan
 # ---------------------------------------------------------------------------------------------
-ROBUST_MAX_ROWS = 16  # rows the device kernels take (ops.trimmed_mean_into / krum_into / geometric_median_into)
+ROBUST_MAX_ROWS = 16  # rows the device kernels take (ops.trimmed_mean_into / krum_into / geometric_median_into / bulyan_into)
 
 
 @traced("aggregate_trimmed_mean")
@@ -984,6 +984,22 @@ def aggregate_geometric_median(fed: Federation, arrived: Dict[str, Tuple[float, 
     fed.record("aggregate", time.perf_counter() - t0)
 
 
+@traced("aggregate_bulyan")
+def aggregate_bulyan(fed: Federation, arrived: Dict[str, Tuple[float, Any]], aggregator) -> None:
+    """Bulyan over the trainers' models on the device (host math: ``Bulyan.aggregate``): the
+    all-gather of :func:`aggregate_median`, then ``ops.bulyan_into`` — Krum's distances, K − 2f rows
+    picked by iterated Krum and, per coordinate, the mean of the K − 4f picked values closest to
+    their median written into every local peer, the selection never leaving the device on the
+    round's path. ``K < 4f + 3`` with K this round's trainers raises the host aggregator's
+    ``ValueError`` on every rank, before any collective. Every rank reduces the same gathered buffer
+    with the same grid, so all of them pick the same peers, bit for bit. Afterwards every local
+    node's aggregator carries ``last_selection = (trainer addresses in row order, coef)``; ``coef``
+    is the device tensor (reading it is the caller's synchronisation), 0 for a rejected peer."""
+    t0 = time.perf_counter()
+    fed.run_aggregation(lambda: _robust(fed, arrived, aggregator, "bulyan"))
+    fed.record("aggregate", time.perf_counter() - t0)
+
+
 def _trim_count(aggregator, k: int) -> int:
     trim = int(np.floor(aggregator.beta * k))
     if 2 * trim >= k:
@@ -992,13 +1008,15 @@ def _trim_count(aggregator, k: int) -> int:
 
 
 def _robust_into(kind: str, aggregator, rows, outs, ws):
-    """The device op of ``kind``; Krum and the geometric median return their ``coef`` device tensor."""
+    """The device op of ``kind``; Krum, the geometric median and Bulyan return their ``coef`` device tensor."""
     with torch.no_grad():
         if kind == "trimmed_mean":
             ops.trimmed_mean_into(rows, outs, _trim_count(aggregator, len(rows)))
             return None
         if kind == "geometric_median":
             return ops.geometric_median_into(rows, outs, ws, aggregator.iters, aggregator.nu)[0]
+        if kind == "bulyan":
+            return ops.bulyan_into(rows, outs, aggregator.f)[2]
         return ops.krum_into(rows, outs, ws, aggregator.f, aggregator.m)[2]
 
 
@@ -1013,8 +1031,8 @@ def _row_fns(learners, kind: str):
     ``get_parameters()`` — the whole ``state_dict``, BatchNorm's integer ``num_batches_tracked``
     included — so the Krum row carries those counters too, behind everything that is unpacked: the
     device and the host then score the same vector and select the same peers. The geometric median
-    measures distances too, and takes the same rows."""
-    whole = kind in ("krum", "geometric_median")
+    and Bulyan measure distances too, and take the same rows."""
+    whole = kind in ("krum", "geometric_median", "bulyan")
     live = all(len(state_tensors(lr)) == 1 and not (whole and _int_buffers(lr)) for lr in learners)
     if live:
         return True, lambda lr: lr.flat_params()
@@ -1026,7 +1044,7 @@ def _row_fns(learners, kind: str):
 def _publish_selection(fed: Federation, addrs, aggregator, order, coef) -> None:
     if coef is None:
         return
-    # Krum publishes a selection, the geometric median its weights
+    # Krum and Bulyan publish a selection, the geometric median its weights
     attr = "last_weights" if getattr(aggregator, "collective_kind", None) == "geometric_median" else "last_selection"
     setattr(aggregator, attr, (list(order), coef))
     for a in addrs:
@@ -1053,6 +1071,8 @@ def _robust(fed: Federation, arrived: Dict[str, Tuple[float, Any]], aggregator, 
         return
     if kind == "trimmed_mean":
         _trim_count(aggregator, len(order))  # the same K on every rank: all of them raise, or none
+    if kind == "bulyan":
+        ops.bulyan_check(len(order), aggregator.f)  # likewise
     live, row_of = _row_fns(list(learners.values()), kind)
 
     def reduce_rows(rows) -> None:
@@ -1080,7 +1100,7 @@ def _robust(fed: Federation, arrived: Dict[str, Tuple[float, Any]], aggregator, 
 
 
 def _mesh_robust(fed: Federation, arrived: Dict[str, Tuple[float, Any]], aggregator, kind: str) -> None:
-    """Trimmed mean / Krum / geometric median over a device mesh, in the manner of ``_mesh_median``: every device
+    """Trimmed mean / Krum / geometric median / Bulyan over a device mesh, in the manner of ``_mesh_median``: every device
     packs its trainers' rows ([k_max, n], zero-padded), ONE mesh all-gather, then per device the op
     into a result vector unpacked into its peers. Every device reduces the same gathered rows in the
     same order, so a Krum selection is the same on all of them."""
@@ -1095,6 +1115,8 @@ def _mesh_robust(fed: Federation, arrived: Dict[str, Tuple[float, Any]], aggrega
         return
     if kind == "trimmed_mean":
         _trim_count(aggregator, len(order))
+    if kind == "bulyan":
+        ops.bulyan_check(len(order), aggregator.f)
     _, row_of = _row_fns(learners, kind)
     kmax = max(counts)
     n = row_of(learners[0]).numel()

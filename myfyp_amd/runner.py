@@ -24,7 +24,7 @@ One description drives every experiment the examples, the CLI and the FYP harnes
         name: MLP               # MLP | LeNet5 | ResNet18, or package + model_build_fn
         params: {}              # + compression: {ptq: {dtype: float16}, topk: {k: 0.1}, zlib: {level: 6}}
       aggregator:
-        name: FedAvg            # FedAvg | FedMedian | Scaffold | FedProx | Krum | TrimmedMean | GeometricMedian
+        name: FedAvg            # FedAvg | FedMedian | Scaffold | FedProx | Krum | TrimmedMean | GeometricMedian | Bulyan
         params: {}
       attack: {node: 1, kind: sign_flip, sigma: 0.1, persistent: false}
       faults: [{node: 2, kill_at: TrainStage, round: 1}]
@@ -69,6 +69,7 @@ _AGGREGATORS = {
     "trimmedmean": ("myfyp_amd.learning.aggregators.trimmed_mean", "TrimmedMean"),
     "geometricmedian": ("myfyp_amd.learning.aggregators.geometric_median", "GeometricMedian"),
     "geomedian": ("myfyp_amd.learning.aggregators.geometric_median", "GeometricMedian"),
+    "bulyan": ("myfyp_amd.learning.aggregators.bulyan", "Bulyan"),
     "neighboravg": ("myfyp_amd.learning.aggregators.neighbor_avg", "NeighborAvg"),
 }
 _MODELS = {"mlp": "MLP", "lenet5": "LeNet5", "lenet": "LeNet5", "resnet18": "ResNet18", "resnet": "ResNet18"}
