@@ -3,7 +3,17 @@
 #include <stdint.h>
 #include "common.h"
 
-void fl_weighted_sum(float* out, const uint64_t* srcs, const float* w, int K, int64_t n, hipStream_t s);
+// Contract of the weighted sums, FedAvg, broadcast and mixing launchers below:
+//  * rows of weight 0 are never read (fl_weighted_sum, fl_stacked_weighted_sum, fl_fedavg_reduce,
+//    fl_fedavg_local): a peer that did not train may hold anything, NaN included;
+//  * any 4-byte-aligned pointer and any ld >= n is accepted, and the result does not depend on
+//    alignment: the 16-byte vector path runs only when ld % 4 == 0 and every base pointer (out,
+//    out2, stacked, src) is 16-byte aligned, the scalar path otherwise. fl_weighted_sum cannot see
+//    its row pointers (they live in device memory): the caller says whether all of them are
+//    16-byte aligned. The one exception is fl_neighbor_mix, which has no scalar path: it needs
+//    ld % 4 == 0, ld >= 4·ceil(n/4) and a 16-byte-aligned base (myfyp_neighbor_mix_stacked
+//    rejects anything else with status 2).
+void fl_weighted_sum(float* out, const uint64_t* srcs, const float* w, int K, int64_t n, bool srcs_aligned16, hipStream_t s);
 void fl_stacked_weighted_sum(float* out, const float* stacked, int P, int64_t n, int64_t ld, const float* w, float scale, hipStream_t s);
 void fl_broadcast_rows(float* stacked, const float* src, int P, int64_t n, int64_t ld, const float* mask, hipStream_t s);
 #define FEDAVG_MAX_PEERS 64

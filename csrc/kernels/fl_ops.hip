@@ -13,33 +13,49 @@ static inline unsigned grid_for(int64_t n_vec) {
   return (unsigned)g;
 }
 
-// out[i] = Σ_k w[k] · src_k[i]   (src pointers in a device array)
+// Vector paths. A kernel below takes its 16-byte (float4) path only when its launcher found the row
+// stride a multiple of 4 floats and every base pointer 16-byte aligned (vec_ok); otherwise the
+// scalar path covers every element. Both paths add the rows in the same order with the same
+// arithmetic, so a result does not depend on where its buffers lie. The decision is made once per
+// launch on the host.
+template <typename... Ptr>
+static inline bool vec_ok(int64_t ld, Ptr... ptrs) {
+  uintptr_t bits = 0;
+  ((bits |= reinterpret_cast<uintptr_t>(ptrs)), ...);
+  return (ld % 4) == 0 && (bits & 15u) == 0;
+}
+
+// out[i] = Σ_k w[k] · src_k[i]   (src pointers in a device array; the caller, who holds them,
+// says whether they are all 16-byte aligned). Rows of weight 0 are never read.
+template <bool VEC>
 __global__ __launch_bounds__(FL_BLOCK) void k_weighted_sum(float* __restrict__ out, const uint64_t* __restrict__ srcs, const float* __restrict__ w, int K,
                                                             int64_t n) {
-  const int64_t n4 = n / 4;
+  const int64_t n4 = VEC ? n / 4 : 0;
   const int64_t stride = (int64_t)gridDim.x * FL_BLOCK;
   for (int64_t i = blockIdx.x * FL_BLOCK + threadIdx.x; i < n4; i += stride) {
     float4 acc = {0.f, 0.f, 0.f, 0.f};
     for (int k = 0; k < K; ++k) {
-      const float4 v = reinterpret_cast<const float4*>(srcs[k])[i];
       const float wk = w[k];
+      if (wk == 0.f) continue;
+      const float4 v = reinterpret_cast<const float4*>(srcs[k])[i];
       acc.x += wk * v.x; acc.y += wk * v.y; acc.z += wk * v.z; acc.w += wk * v.w;
     }
     reinterpret_cast<float4*>(out)[i] = acc;
   }
   for (int64_t i = n4 * 4 + blockIdx.x * FL_BLOCK + threadIdx.x; i < n; i += stride) {
     float acc = 0.f;
-    for (int k = 0; k < K; ++k) acc += w[k] * reinterpret_cast<const float*>(srcs[k])[i];
+    for (int k = 0; k < K; ++k)
+      if (w[k] != 0.f) acc += w[k] * reinterpret_cast<const float*>(srcs[k])[i];
     out[i] = acc;
   }
 }
 
-// out[i] = scale · Σ_p w[p] · stacked[p*ld + i]   (co-located peers, [P][ld] buffer)
+// out[i] = scale · Σ_p w[p] · stacked[p*ld + i]   (co-located peers, [P][ld] buffer). Rows of
+// weight 0 are never read (peers that did not train may hold anything).
 __global__ __launch_bounds__(FL_BLOCK) void k_stacked_weighted_sum(float* __restrict__ out, const float* __restrict__ stacked, int P, int64_t n, int64_t ld,
-                                                                    const float* __restrict__ w, float scale) {
+                                                                    const float* __restrict__ w, float scale, bool vec) {
   const int64_t n4 = n / 4;
   const int64_t stride = (int64_t)gridDim.x * FL_BLOCK;
-  const bool vec = (ld % 4) == 0;
   if (vec) {
     for (int64_t i = blockIdx.x * FL_BLOCK + threadIdx.x; i < n4; i += stride) {
       float4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -55,19 +71,20 @@ __global__ __launch_bounds__(FL_BLOCK) void k_stacked_weighted_sum(float* __rest
   }
   for (int64_t i = (vec ? n4 * 4 : 0) + blockIdx.x * FL_BLOCK + threadIdx.x; i < n; i += stride) {
     float acc = 0.f;
-    for (int p = 0; p < P; ++p) acc += w[p] * stacked[p * ld + i];
+    for (int p = 0; p < P; ++p)
+      if (w[p] != 0.f) acc += w[p] * stacked[p * ld + i];
     out[i] = acc * scale;
   }
 }
 
 // stacked[p*ld + i] = src[i] for rows with mask[p] != 0 (mask null = all rows)
 __global__ __launch_bounds__(FL_BLOCK) void k_broadcast_rows(float* __restrict__ stacked, const float* __restrict__ src, int P, int64_t n, int64_t ld,
-                                                              const float* __restrict__ mask) {
+                                                              const float* __restrict__ mask, bool vec) {
   const int p = blockIdx.y;
   if (mask != nullptr && mask[p] == 0.f) return;
   const int64_t stride = (int64_t)gridDim.x * FL_BLOCK;
   float* dst = stacked + p * ld;
-  if ((ld % 4) == 0) {
+  if (vec) {
     const int64_t n4 = n / 4;
     for (int64_t i = blockIdx.x * FL_BLOCK + threadIdx.x; i < n4; i += stride)
       reinterpret_cast<float4*>(dst)[i] = reinterpret_cast<const float4*>(src)[i];
@@ -87,12 +104,12 @@ __global__ __launch_bounds__(FL_BLOCK) void k_broadcast_rows(float* __restrict__
 // by the same pass instead of a separate device copy behind it
 __global__ __launch_bounds__(FL_BLOCK) void k_fedavg_reduce(float* __restrict__ out, float* __restrict__ wsum_slot, const float* __restrict__ stacked,
                                                              int P, int64_t n, int64_t ld, FedAvgWeights w, float* __restrict__ out2,
-                                                             float* __restrict__ wsum2) {
+                                                             float* __restrict__ wsum2, bool vec) {
   const int64_t stride = (int64_t)gridDim.x * FL_BLOCK;
   const int64_t t0 = blockIdx.x * FL_BLOCK + threadIdx.x;
   if (t0 == 0 && wsum_slot != nullptr) *wsum_slot = w.wsum;
   if (t0 == 0 && wsum2 != nullptr) *wsum2 = w.wsum;
-  if ((ld % 4) == 0) {
+  if (vec) {
     const int64_t n4 = n / 4;
     for (int64_t i = t0; i < n4; i += stride) {
       float4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -124,13 +141,13 @@ __global__ __launch_bounds__(FL_BLOCK) void k_fedavg_reduce(float* __restrict__ 
 }
 
 __global__ __launch_bounds__(FL_BLOCK) void k_fedavg_apply(float* __restrict__ stacked, const float* __restrict__ out, const float* __restrict__ wsum_slot,
-                                                            int P, int64_t n, int64_t ld, unsigned long long mask) {
+                                                            int P, int64_t n, int64_t ld, unsigned long long mask, bool vec) {
   const int p = blockIdx.y;
   if (!((mask >> p) & 1ull)) return;
   const float inv = 1.f / fmaxf(*wsum_slot, 1e-12f);
   const int64_t stride = (int64_t)gridDim.x * FL_BLOCK;
   float* dst = stacked + p * ld;
-  if ((ld % 4) == 0) {
+  if (vec) {
     const int64_t n4 = n / 4;
     for (int64_t i = blockIdx.x * FL_BLOCK + threadIdx.x; i < n4; i += stride) {
       float4 v = reinterpret_cast<const float4*>(out)[i];
@@ -146,10 +163,10 @@ __global__ __launch_bounds__(FL_BLOCK) void k_fedavg_apply(float* __restrict__ s
 // Single-rank FedAvg (no all-reduce between reduce and apply): each thread forms the weighted mean
 // of its coordinates over the rows and writes it into every masked row — one launch instead of two.
 __global__ __launch_bounds__(FL_BLOCK) void k_fedavg_local(float* __restrict__ stacked, int P, int64_t n, int64_t ld, FedAvgWeights w,
-                                                           unsigned long long mask) {
+                                                           unsigned long long mask, bool vec) {
   const int64_t stride = (int64_t)gridDim.x * FL_BLOCK;
   const float inv = 1.f / fmaxf(w.wsum, 1e-12f);
-  if ((ld % 4) == 0) {
+  if (vec) {
     const int64_t n4 = n / 4;
     for (int64_t i = blockIdx.x * FL_BLOCK + threadIdx.x; i < n4; i += stride) {
       float4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -182,18 +199,19 @@ __global__ __launch_bounds__(FL_BLOCK) void k_fedavg_local(float* __restrict__ s
 }
 
 void fl_fedavg_local(float* stacked, int P, int64_t n, int64_t ld, const FedAvgWeights& w, unsigned long long mask, hipStream_t s) {
-  hipLaunchKernelGGL(k_fedavg_local, dim3(grid_for((n + 3) / 4)), dim3(FL_BLOCK), 0, s, stacked, P, n, ld, w, mask);
+  hipLaunchKernelGGL(k_fedavg_local, dim3(grid_for((n + 3) / 4)), dim3(FL_BLOCK), 0, s, stacked, P, n, ld, w, mask, vec_ok(ld, stacked));
 }
 
 void fl_fedavg_reduce(float* out, float* wsum_slot, const float* stacked, int P, int64_t n, int64_t ld, const FedAvgWeights& w, hipStream_t s,
                       float* out2, float* wsum2) {
-  hipLaunchKernelGGL(k_fedavg_reduce, dim3(grid_for((n + 3) / 4)), dim3(FL_BLOCK), 0, s, out, wsum_slot, stacked, P, n, ld, w, out2, wsum2);
+  hipLaunchKernelGGL(k_fedavg_reduce, dim3(grid_for((n + 3) / 4)), dim3(FL_BLOCK), 0, s, out, wsum_slot, stacked, P, n, ld, w, out2, wsum2,
+                     vec_ok(ld, out, out2, stacked));
 }
 
 void fl_fedavg_apply(float* stacked, const float* out, const float* wsum_slot, int P, int64_t n, int64_t ld, unsigned long long mask, hipStream_t s) {
   unsigned gx = grid_for((n + 3) / 4);
   if (gx > 256) gx = 256;
-  hipLaunchKernelGGL(k_fedavg_apply, dim3(gx, P), dim3(FL_BLOCK), 0, s, stacked, out, wsum_slot, P, n, ld, mask);
+  hipLaunchKernelGGL(k_fedavg_apply, dim3(gx, P), dim3(FL_BLOCK), 0, s, stacked, out, wsum_slot, P, n, ld, mask, vec_ok(ld, stacked, out));
 }
 
 // Delayed averaging (opt-in): land the previous round's average as a correction and take the new
@@ -934,16 +952,19 @@ __global__ __launch_bounds__(FL_BLOCK) void k_scale_add_noise(float* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------------
-void fl_weighted_sum(float* out, const uint64_t* srcs, const float* w, int K, int64_t n, hipStream_t s) {
-  hipLaunchKernelGGL(k_weighted_sum, dim3(grid_for(n / 4 + 1)), dim3(FL_BLOCK), 0, s, out, srcs, w, K, n);
+void fl_weighted_sum(float* out, const uint64_t* srcs, const float* w, int K, int64_t n, bool srcs_aligned16, hipStream_t s) {
+  const dim3 g(grid_for(n / 4 + 1)), b(FL_BLOCK);
+  if (srcs_aligned16 && vec_ok(0, out)) hipLaunchKernelGGL(k_weighted_sum<true>, g, b, 0, s, out, srcs, w, K, n);
+  else hipLaunchKernelGGL(k_weighted_sum<false>, g, b, 0, s, out, srcs, w, K, n);
 }
 void fl_stacked_weighted_sum(float* out, const float* stacked, int P, int64_t n, int64_t ld, const float* w, float scale, hipStream_t s) {
-  hipLaunchKernelGGL(k_stacked_weighted_sum, dim3(grid_for(n / 4 + 1)), dim3(FL_BLOCK), 0, s, out, stacked, P, n, ld, w, scale);
+  hipLaunchKernelGGL(k_stacked_weighted_sum, dim3(grid_for(n / 4 + 1)), dim3(FL_BLOCK), 0, s, out, stacked, P, n, ld, w, scale,
+                     vec_ok(ld, out, stacked));
 }
 void fl_broadcast_rows(float* stacked, const float* src, int P, int64_t n, int64_t ld, const float* mask, hipStream_t s) {
   unsigned gx = grid_for(n / 4 + 1);
   if (gx > 256) gx = 256;
-  hipLaunchKernelGGL(k_broadcast_rows, dim3(gx, P), dim3(FL_BLOCK), 0, s, stacked, src, P, n, ld, mask);
+  hipLaunchKernelGGL(k_broadcast_rows, dim3(gx, P), dim3(FL_BLOCK), 0, s, stacked, src, P, n, ld, mask, vec_ok(ld, stacked, src));
 }
 void fl_coordinate_median(const OutPtrs& outs, int P, const RowPtrs& rows, int K, int64_t n, hipStream_t s) {
   const dim3 g(grid_for(n)), b(FL_BLOCK);
@@ -1077,8 +1098,9 @@ void fl_scaffold_apply(const OutPtrs& outs, int P, const float* x_start, const f
 }
 void fl_opt_step(float* param, const float* grad, float* m, float* v, bf16* shadow, int64_t n, const OptParams& o, int step, const float* anchor,
                  const float* cg, const float* cl, hipStream_t s) {
-  const float bc1 = 1.f - powf(o.beta1, (float)step);
-  const float bc2s = sqrtf(1.f - powf(o.beta2, (float)step));
+  // in double from the float betas, rounded once: in float, 1 - powf(beta2, t) keeps only ~15 bits at small t
+  const float bc1 = (float)(1.0 - pow((double)o.beta1, (double)step));
+  const float bc2s = (float)sqrt(1.0 - pow((double)o.beta2, (double)step));
   hipLaunchKernelGGL(k_opt_step, dim3(grid_for(n)), dim3(FL_BLOCK), 0, s, param, grad, m, v, shadow, n, o, bc1, bc2s, anchor, cg, cl);
 }
 void fl_scale_add_noise(float* t, int64_t n, float scale, float sigma, uint64_t seed, hipStream_t s) {
@@ -1092,7 +1114,7 @@ extern "C" int myfyp_warm_fl_ops() {
   hipFuncAttributes attr;
   // the robust aggregators' launches of the headline peer count (8) resolve here too, so a first
   // Krum / trimmed-mean / geometric-median / Bulyan round pays no lookup behind a running epoch
-  const void* fns[] = {reinterpret_cast<const void*>(&k_weighted_sum),
+  const void* fns[] = {reinterpret_cast<const void*>(&k_weighted_sum<true>),
                        reinterpret_cast<const void*>(&k_trimmed_mean<8>),
                        reinterpret_cast<const void*>(&k_pairwise_sqdist<8, true>),
                        reinterpret_cast<const void*>(&k_krum_select),

@@ -853,8 +853,9 @@ int myfyp_version() { return 1; }
 const char* myfyp_last_error() { return g_last_error.c_str(); }
 
 // ------------------------------------------------------------------------------ generic FL ops
-int myfyp_weighted_sum(float* out, const uint64_t* srcs, const float* w, int K, int64_t n, void* stream) {
-  fl_weighted_sum(out, srcs, w, K, n, (hipStream_t)stream);
+// srcs_aligned16: every row pointer in srcs (device memory) is 16-byte aligned; 0 takes the scalar kernel
+int myfyp_weighted_sum(float* out, const uint64_t* srcs, const float* w, int K, int64_t n, int srcs_aligned16, void* stream) {
+  fl_weighted_sum(out, srcs, w, K, n, srcs_aligned16 != 0, (hipStream_t)stream);
   CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -951,10 +952,11 @@ int myfyp_fedavg_stacked_local(float* stacked, int P, int64_t n, int64_t ld, con
 }
 // Topology mixing of a stacked group in one launch. w_host is the dense [P][P] mixing matrix
 // (row p: the weights of the sources of row p, already renormalised); rows of an all-zero matrix
-// row are left untouched. ld must be a multiple of 4 (stacked rows are padded to 64 floats).
+// row are left untouched. ld must be a multiple of 4 (stacked rows are padded to 64 floats) and the
+// base 16-byte aligned: the kernel has no scalar path.
 int myfyp_neighbor_mix_stacked(float* stacked, int P, int64_t n, int64_t ld, const float* w_host, void* stream) {
-  if (P < 1 || P > MIX_MAX_PEERS || (ld % 4) != 0 || ld < ((n + 3) / 4) * 4) {
-    g_last_error = "neighbor_mix_stacked: 1..16 rows, ld a multiple of 4 covering n";
+  if (P < 1 || P > MIX_MAX_PEERS || (ld % 4) != 0 || ld < ((n + 3) / 4) * 4 || (reinterpret_cast<uintptr_t>(stacked) & 15u) != 0) {
+    g_last_error = "neighbor_mix_stacked: 1..16 rows, ld a multiple of 4 covering n, a 16-byte-aligned base";
     return 2;
   }
   MixPlan m{};

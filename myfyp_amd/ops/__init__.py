@@ -86,7 +86,8 @@ def weighted_average(param_lists: Sequence[Sequence[torch.Tensor]], norm_weights
         for layer in range(len(param_lists[0])):
             acc = torch.zeros_like(param_lists[0][layer], dtype=torch.float64)
             for p, w in zip(param_lists, norm_weights):
-                acc += p[layer].double() * w
+                if w != 0:  # as on the device: a model of weight 0 is never read
+                    acc += p[layer].double() * w
             out.append(acc.to(param_lists[0][layer].dtype))
         return out
     lib = _lib()
@@ -95,15 +96,20 @@ def weighted_average(param_lists: Sequence[Sequence[torch.Tensor]], norm_weights
         srcs = [p[layer].contiguous().float() for p in param_lists]
         dst = torch.empty_like(srcs[0])
         ptrs = torch.tensor([s.data_ptr() for s in srcs], dtype=torch.int64, device=dev)
-        _native.check(lib.myfyp_weighted_sum(dst.data_ptr(), ptrs.data_ptr(), w.data_ptr(), k, dst.numel(), _stream()), "weighted_sum")
+        # a layer view at an odd offset of a flat buffer is only 4-byte aligned: the kernel reads its row
+        # pointers from device memory, so the vector path is chosen here, from the pointers in hand
+        aligned = all(s.data_ptr() % 16 == 0 for s in srcs)
+        _native.check(lib.myfyp_weighted_sum(dst.data_ptr(), ptrs.data_ptr(), w.data_ptr(), k, dst.numel(), int(aligned), _stream()), "weighted_sum")
         out.append(dst.to(param_lists[0][layer].dtype))
     return out
 
 
 def stacked_weighted_sum(stacked: torch.Tensor, weights: torch.Tensor, out: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
-    """``out[n] = scale · Σ_p weights[p] · stacked[p, n]`` for a ``[P, N]`` fp32 buffer."""
+    """``out[n] = scale · Σ_p weights[p] · stacked[p, n]`` for a ``[P, N]`` fp32 buffer. Rows of
+    weight 0 are never read (a peer that did not train may hold anything)."""
     if stacked.device.type != "cuda":
-        out.copy_((weights.view(-1, 1).to(stacked.dtype) * stacked).sum(0) * scale)
+        keep = weights != 0
+        out.copy_((weights[keep].view(-1, 1).to(stacked.dtype) * stacked[keep]).sum(0) * scale)
         return out
     lib = _lib()
     p, n = stacked.shape

@@ -35,7 +35,7 @@ _SIGNATURES = {
     "myfyp_version": (c_int, []),
     "myfyp_last_error": (ctypes.c_char_p, []),
     # aggregation
-    "myfyp_weighted_sum": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
+    "myfyp_weighted_sum": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p]),
     "myfyp_stacked_weighted_sum": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, c_float, c_void_p]),
     "myfyp_broadcast_rows": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p]),
     "myfyp_coordinate_median": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p]),
