@@ -29,7 +29,8 @@ hipError_t mlp_launch_persistent_epoch(const MLPArgs& a, const MLPPersistBufs& p
 struct MLPPersistF32Bufs {
   float* h1x;       // [P][Bpad][256]      owner g -> heads: H1 columns 16g..16g+15
   float* plx;       // [P][8][Bpad*16][2]  head hd -> heads: partial logits over its H2 slice (sized for (value, tag) pairs)
-  float* dh2x;      // [P][2][Bpad][128][2] head hd -> owners: dH2 columns 16hd..16hd+15 (step parity; sized for pairs)
+  float* dh2x;      // [P][2][Bpad][128][2] head hd -> owners: dH2 columns 16hd..16hd+15 (step parity; sized for pairs);
+                    // dh2_frag: the first half of each parity slab as [8 hd][Bpad / 16][64 lanes] float4 (see below)
   unsigned* gen;    // [P] epoch generation (advanced by every completed epoch; it tagged the LL pairs, nothing reads it now)
   unsigned* flags;  // [P][32][32] one 128-B line per flag (16 H1, 8 PL, 8 dH2); zeroed per launch
   size_t flag_bytes;
@@ -43,6 +44,8 @@ struct MLPPersistF32Bufs {
   int c2_straight;  // layout 1, K split 1: owners may take C2's straight-line body (set at launch: MYFYP_F32_C2_STRAIGHT)
   int k24;          // ... and the wave that owns K step 24 keeps its state in registers over the step loop (set at launch
                     // where it applies: MYFYP_F32_K24; the launch then takes the K24 instantiation)
+  int dh2_frag;     // layout 1: the heads publish dH2 as the owners' MFMA A fragments, dh2f[parity][hd][mt][lane] float4, and
+                    // the owners load them straight into registers (set at launch: MYFYP_F32_DH2_FRAG; 0: the [b][128] tile)
 };
 
 int mlp_plain_pub_mode();  // single-XCD hand-off mode of the persistent kernels (MYFYP_F32_PLAIN_PUB / mlp_set_plain_pub)

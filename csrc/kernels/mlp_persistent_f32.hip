@@ -486,11 +486,20 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
     const __amdgpu_buffer_rsrc_t rd = rsrc_of(pb.dh2x + ((int64_t)p * 2 + (tp & 1)) * BP * PD2 * 2, BP * PD2 * 8);
     int lr = lane;
     asm volatile("" : "+v"(lr));
-    const int ro = 4 * ((lr >> 4) * PD2 + 16 * wave + (lr & 15));
+    // tile: dH2[4kb + h][16 wave + c] at row stride PD2. Fragment image (pb.dh2_frag, see head32): the
+    // same element is word c & 3 of entry [hd = wave][mt = kb / 4][lane (c >> 2) 16 + 4 (kb & 3) + h]
+    // (one step of kb is 4 lanes = 64 bytes on, one batch tile 64 lanes = 1 KB)
     const float* h1p = sH1 + (tp & 1) * BP * 16;
     float av[BP / 4];
+    if (!RH && pb.dh2_frag != 0) {
+      const int ro = 4 * (((wave * MT) * 64 + ((lr & 15) >> 2) * 16 + (lr >> 4)) * 4 + (lr & 3));
 #pragma unroll
-    for (int kb = 0; kb < BP / 4; ++kb) av[kb] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rd, ro + 4 * 4 * kb * PD2, 0, 16));
+      for (int kb = 0; kb < BP / 4; ++kb) av[kb] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rd, ro + 1024 * (kb >> 2) + 64 * (kb & 3), 0, 16));
+    } else {
+      const int ro = 4 * ((lr >> 4) * PD2 + 16 * wave + (lr & 15));
+#pragma unroll
+      for (int kb = 0; kb < BP / 4; ++kb) av[kb] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rd, ro + 4 * 4 * kb * PD2, 0, 16));
+    }
     f32x4 acc = zero4();
 #pragma unroll
     for (int kb = 0; kb < BP / 4; ++kb) acc = mfma_f32(av[kb], h1p[(4 * kb + h) * 16 + c], acc);
@@ -781,7 +790,16 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
         *reinterpret_cast<float4*>(sH1c + b * 16 + c4) = float4{fmaxf(sum.x, 0.f), fmaxf(sum.y, 0.f), fmaxf(sum.z, 0.f), fmaxf(sum.w, 0.f)};
       }
     }
-    {
+    // dH2 as the heads' fragment image (layout 1, MYFYP_F32_DH2_FRAG; see head32): head `wave` wrote
+    // this wave's A operands of every batch tile in lane order, so they come straight into registers,
+    // one coalesced 1 KB load per tile, with no LDS staging and none of its two barriers. The lane is
+    // the step's laundered one (an address hoisted across the step loop would be spilled).
+    const bool frag = !RH && pb.dh2_frag != 0;
+    float4 avf[MT];
+    if (frag) {
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) avf[mt] = ld_sc1_16(r_dh2, ((wave * MT + mt) * 64 + (tv & 63)) * 16);
+    } else {
       float4 v[BP / 16];
 #pragma unroll
       for (int k = 0; k < BP / 16; ++k) v[k] = ld_sc1_16(r_dh2, (tv + NT * k) * 16);  // BP x 128 fp32 = BP*32 chunks
@@ -790,19 +808,24 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
         const int e = tv + NT * k;
         *reinterpret_cast<float4*>(sDH2 + (e >> 5) * LDD + 4 * (e & 31)) = v[k];
       }
+      lds_barrier();
     }
-    lds_barrier();
     if (sOk[1] == 0) return;  // (never taken: see sOk[1] above)
     // C1: dH1 partials — wave w sums its 16 o2 rows (k order o2 = 16w + 4h + ks)
     {
       f32x4 acc1[MT];
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) {
-        const float4 av = *reinterpret_cast<const float4*>(sDH2 + (16 * mt + c) * LDD + 16 * wave + 4 * h);
+      auto dh1_chain = [&](const float4 av) __attribute__((always_inline)) {
         f32x4 acc = mfma_f32(av.x, w2c[0], zero4());
         acc = mfma_f32(av.y, w2c[1], acc);
         acc = mfma_f32(av.z, w2c[2], acc);
-        acc1[mt] = mfma_f32(av.w, w2c[3], acc);
+        return mfma_f32(av.w, w2c[3], acc);
+      };
+      if (frag) {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) acc1[mt] = dh1_chain(avf[mt]);
+      } else {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) acc1[mt] = dh1_chain(*reinterpret_cast<const float4*>(sDH2 + (16 * mt + c) * LDD + 16 * wave + 4 * h));
       }
       // layout 3: dW2[16w + 4h + i][16cg + c] over the batch (the same k-ordered chain as the
       // deferred replica update), from the staged dH2 before the partials overwrite it
@@ -812,7 +835,12 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
 #pragma unroll
         for (int kb = 0; kb < BP / 4; ++kb) dw2 = mfma_f32(sDH2[(4 * kb + h) * LDD + 16 * wave + c], h1p[(4 * kb + h) * 16 + c], dw2);
       }
-      lds_barrier();  // every wave has read its dH2 fragments before the partials overwrite them
+      // staged tile: every wave has read its dH2 fragments before the partials overwrite them (sRed
+      // overlays sDH2). Fragment image: nothing was staged, and sRed's previous readers are behind a
+      // workgroup barrier already: the reduction of step t - 1's C1 ran before that step's lds_barrier
+      // in front of C2, and h1_publish's reduction (this step's A, or step t - 1's C2 with the fused
+      // forward) before publish_p's __syncthreads(); wg_wait's __syncthreads() above follows both.
+      if (!frag) lds_barrier();
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) sRed[(wave * MT + mt) * 64 + lane] = acc1[mt];
       if (RH) {
@@ -1351,12 +1379,28 @@ __device__ void head32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, int
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) acc = mfma_f32(sDlog[(16 * wave + c) * LD16 + 4 * ks + h], sW3[(4 * ks + h) * LD16 + c], acc);
       float* dst = pb.dh2x + ((int64_t)p * 2 + (t & 1)) * BP * PD2 * 2;
+      if (pb.dh2_frag != 0) {
+        // fragment image (MYFYP_F32_DH2_FRAG): dh2f[hd][mt = wave][lane] = dH2[16 wave + c][16 hd + 4h ..
+        // + 3], the A operands of owner wave hd's four dH1 MFMAs on batch tile mt, so that an owner
+        // loads them straight into registers (one coalesced 1 KB access per wave and tile). This wave
+        // wrote all 16 rows of its tile itself: the read-back needs its own LDS stores only, no barrier.
+        // One 16-byte store per lane in front of the flag instead of four 4-byte ones.
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int b = 16 * wave + 4 * h + i;
-        const float v = sH2[b * LD16 + c] > 0.f ? acc[i] : 0.f;
-        sDH2[b * LD16 + c] = v;
-        persist::pub32(pb.plain_x, dst + b * PD2 + 16 * hd + c, v);  // (XR: written through to every XCD)
+        for (int i = 0; i < 4; ++i) {
+          const int b = 16 * wave + 4 * h + i;
+          sDH2[b * LD16 + c] = sH2[b * LD16 + c] > 0.f ? acc[i] : 0.f;
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        const float4 fr = *reinterpret_cast<const float4*>(sDH2 + (16 * wave + c) * LD16 + 4 * h);
+        persist::pub128(pb.plain_x, dst, BP * PD2 * 4, ((hd * MT + wave) * 64 + (tv & 63)) * 16, __builtin_bit_cast(u32x4, fr));  // (XR: written through)
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int b = 16 * wave + 4 * h + i;
+          const float v = sH2[b * LD16 + c] > 0.f ? acc[i] : 0.f;
+          sDH2[b * LD16 + c] = v;
+          persist::pub32(pb.plain_x, dst + b * PD2 + 16 * hd + c, v);  // (XR: written through to every XCD)
+        }
       }
     }
     persist::publish_p(pb.flags, FPP, p, F_DH2 + hd, target, pb.plain_x);
@@ -2337,10 +2381,32 @@ static int f32_k24_mode() {
 extern "C" int mlp_set_f32_k24(int mode) { return g_k24_override.exchange(mode < 0 ? -1 : mode); }
 extern "C" int mlp_f32_k24_last() { return g_k24_last.load(std::memory_order_relaxed); }
 
+// MYFYP_F32_DH2_FRAG: 1 (default) the heads of layout 1 publish dH2 as the owners' MFMA A fragments
+// (dh2f[parity][hd][mt][lane], one 16-byte store per lane) and the owners' C1 loads them straight into
+// registers, 0 the [b][128] tile staged through LDS (A/B; same bits either way);
+// mlp_set_f32_dh2_frag overrides it (tests; -1: back to the environment). Values above 1 are taken as
+// 1. Heads and owners read it from the same launch argument, pb.dh2_frag. mlp_f32_dh2_frag_last: what
+// the last epoch launch took: 0 for layouts 2 and 3 and with the switch off (-1: none yet).
+static std::atomic<int> g_dh2_frag_override{-1};
+static std::atomic<int> g_dh2_frag_last{-1};
+static int f32_dh2_frag_mode() {
+  const int o = g_dh2_frag_override.load(std::memory_order_relaxed);
+  if (o >= 0) return o;
+  static const int v = [] {
+    const char* e = getenv("MYFYP_F32_DH2_FRAG");
+    return e != nullptr ? atoi(e) : 1;
+  }();
+  return v;
+}
+extern "C" int mlp_set_f32_dh2_frag(int mode) { return g_dh2_frag_override.exchange(mode < 0 ? -1 : mode); }
+extern "C" int mlp_f32_dh2_frag_last() { return g_dh2_frag_last.load(std::memory_order_relaxed); }
+
 hipError_t mlp_launch_persistent_f32_epoch(const MLPArgs& a, const MLPPersistF32Bufs& pb_in, hipStream_t s, bool zero_flags, const int* active) {
   MLPPersistF32Bufs pb = pb_in;
   pb.plain_ok = mlp_plain_pub_mode();
   pb.plain = 0;
+  pb.dh2_frag = f32_dh2_frag_mode() > 0 && f32_variant(a) == 1 ? 1 : 0;
+  g_dh2_frag_last.store(pb.dh2_frag, std::memory_order_relaxed);
   if (zero_flags) {
     hipError_t e = hipMemsetAsync(pb.flags, 0, pb.flag_bytes, s);
     if (e != hipSuccess) return e;

@@ -116,6 +116,8 @@ _SIGNATURES = {
     "mlp_f32_c2_straight_last": (c_int, []),  # 1: the last fp32 layout-1 epoch launch could take it in every wave
     "mlp_set_f32_k24": (c_int, [c_int]),  # K step 24 register-resident on its wave: 1 / 0 (-1: MYFYP_F32_K24)
     "mlp_f32_k24_last": (c_int, []),  # 1: the last fp32 layout-1 epoch launch ran K step 24 from registers
+    "mlp_set_f32_dh2_frag": (c_int, [c_int]),  # dH2 handed over in MFMA fragment order: 1 / 0 (-1: MYFYP_F32_DH2_FRAG)
+    "mlp_f32_dh2_frag_last": (c_int, []),  # 1: the last fp32 epoch launch took it (0: layouts 2 / 3 or switched off)
     "mlp_debug_stamps": (c_int, [c_void_p]),  # only in the -DMLP_STAMPS diagnostics build
     "mlp_debug_persistent_f32_stamps": (c_int, [c_void_p]),  # likewise
 }

@@ -85,6 +85,9 @@ if fused:
     k24_last = getattr(lib, "mlp_f32_k24_last", None)
     if k24_last is not None:
         print("K step 24:", "registers (MYFYP_F32_K24=1)" if k24_last() == 1 else "LDS-resident, guarded")
+frag_last = getattr(lib, "mlp_f32_dh2_frag_last", None)
+if frag_last is not None:
+    print("dH2 hand-off:", "fragment image (MYFYP_F32_DH2_FRAG=1)" if frag_last() == 1 else "[b][128] tile staged through LDS")
 print("owner H1 published -> head H1 seen (us; fused: negative while the head is still in step t - 1):", [round((st[1, t, 1] - st[0, t, 2]) / 100.0, 2) for t in range(2, 10)])
 print("head dH2 published -> owner dH2 seen (us):", [round((st[0, t, 4] - st[1, t, 7]) / 100.0, 2) for t in range(2, 10)])
 print("head PL published -> head PL all seen (us):", [round((st[1, t, 5] - st[1, t, 4]) / 100.0, 2) for t in range(2, 10)])
