@@ -783,11 +783,9 @@ int lenet_fused_supported(int in_c, int in_h, int c1, int c2, int f1, int f2, in
 }
 
 int lenet_fused_step(const LenetArgs* a, int peers, int ipw, void* stream) {
+  if (ipw != 2) return 1;  // the one instantiation (checked first: ipw = 0 must not reach the modulo)
   if (a == nullptr || peers <= 0 || a->B <= 0 || a->B % ipw != 0) return 1;
-  hipStream_t s = (hipStream_t)stream;
-  hipError_t e;
-  if (ipw == 2) e = launch_step<2>(*a, peers, s);
-  else return 1;
+  const hipError_t e = launch_step<2>(*a, peers, (hipStream_t)stream);
   return e == hipSuccess ? 0 : 2;
 }
 
