@@ -4,6 +4,7 @@
     python benchmarks/bench_robust_agg.py --models mlp --repeats 30
     python benchmarks/bench_robust_agg.py --aggregators geometric_median,krum
     python benchmarks/bench_robust_agg.py --aggregators bulyan
+    python benchmarks/bench_robust_agg.py --attack               # ops.collude_into (ALIE, IPM, min-max, min-sum) beside Krum, K = 8 / 16
 
 For each model and aggregator the same 8 co-located peers are aggregated two ways, alternating in
 one process on identical inputs (the rows are restored, untimed, before every call):
@@ -51,6 +52,8 @@ def parse():
     ap.add_argument("--generic-repeats", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--kernel-iters", type=int, default=50, help="back-to-back op calls inside one device-event window")
+    ap.add_argument("--attack", nargs="?", const="all", default=None,
+                    help="time ops.collude_into instead (all, or a comma list of alie,ipm,min_max,min_sum) at K = 8 and 16 honest rows, beside Krum")
     return ap.parse_args()
 
 
@@ -226,6 +229,42 @@ def run_case(model_name: str, agg_name: str, args) -> dict:
         Federation.reset()
 
 
+def run_attack_case(model_name: str, k: int, kinds, args) -> dict:
+    """``ops.collude_into`` (K honest rows, 2 attackers' rows written) next to ``ops.krum_into`` on
+    the same rows in the same process, device events over a window of back-to-back calls. The rows
+    are plain device tensors of the model's trainable size: no nodes, no collective."""
+    import torch
+
+    from myfyp_amd import ops
+
+    dev = torch.device(args.device)
+    if model_name == "mlp":
+        n = 235146
+    else:
+        from myfyp_amd.models import ResNet18
+
+        n = sum(p.numel() for p in ResNet18(seed=0).parameters())
+    g = torch.Generator().manual_seed(1)
+    base = torch.randn(n, generator=g) * 0.05
+    rows = [(base + 1e-3 * (1 + 0.15 * i) * 0.05 * torch.randn(n, generator=g)).to(dev) for i in range(k)]
+    outs = [torch.empty(n, dtype=torch.float32, device=dev) for _ in range(2)]
+    ref = (base + 2e-3 * 0.05 * torch.randn(n, generator=g)).to(dev)
+    w = [1.0] * k
+    it, wu = args.kernel_iters, args.warmup
+    res = {}
+    for kind in kinds:
+        ms = event_ms(dev, lambda: ops.collude_into(rows, outs, kind, z=1.0, ref=ref if kind == "ipm" else None), it, wu)
+        reads = {"alie": 1, "ipm": 1}.get(kind, 3)  # min-max / min-sum read the K rows three times (distances, statistics, write)
+        nbytes = (reads * k + 2 + (1 if kind == "ipm" else 0)) * n * 4
+        res[kind] = {"ms": round(ms, 4), "GBps": round(nbytes / ms / 1e6, 1), "launches": 1 if reads == 1 else 4,
+                     "bytes": f"K rows read {reads}x, 2 rows written" + (", ref read" if kind == "ipm" else "")}
+    ms_sel = event_ms(dev, lambda: ops.krum_into(rows, [], w, 2, 1), it, wu)
+    ms_all = event_ms(dev, lambda: ops.krum_into(rows, outs, w, 2, 1), it, wu)
+    res["krum select only (same rows, same process)"] = {"ms": round(ms_sel, 4), "GBps": round(k * n * 4 / ms_sel / 1e6, 1), "launches": 2, "bytes": "K rows read"}
+    res["krum whole call (same rows, same process)"] = {"ms": round(ms_all, 4), "launches": 3}
+    return {"model": model_name, "op": "collude_into", "honest_rows": k, "outputs": 2, "n": n, "device": str(dev), "kernels": res, "measured": dev.type == "cuda"}
+
+
 def main() -> None:
     args = parse()
     import torch
@@ -236,6 +275,12 @@ def main() -> None:
         raise SystemExit("bench_robust_agg needs a GPU (use --device cpu only to rehearse the plumbing)")
     Settings.DEVICE = args.device
     Settings.LOG_LEVEL = "WARNING"
+    if args.attack:  # the colluding attacks alone, beside Krum on the same rows
+        kinds = ["alie", "ipm", "min_max", "min_sum"] if args.attack == "all" else [a for a in args.attack.split(",") if a]
+        for model_name in [m for m in args.models.split(",") if m]:
+            for k in (8, 16):
+                print(json.dumps(run_attack_case(model_name, k, kinds, args)), flush=True)
+        return
     for model_name in [m for m in args.models.split(",") if m]:
         for agg_name in [a for a in args.aggregators.split(",") if a]:
             print(json.dumps(run_case(model_name, agg_name, args)), flush=True)

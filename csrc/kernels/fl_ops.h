@@ -79,6 +79,17 @@ void fl_bulyan(float* work, const OutPtrs& outs, int P, const RowPtrs& rows, int
                float* coef, hipStream_t s);
 // The last of fl_bulyan's launches alone: coef[K] in device memory marks the K - 2f picked rows.
 void fl_bulyan_mean(const OutPtrs& outs, int P, const RowPtrs& rows, int K, int f, const float* coef, int64_t n, hipStream_t s);
+// Colluding attacks: one crafted row m from the K honest rows 0..K-1, stored into out rows 0..P-1
+// (which are not among the rows). kind: 0 ALIE, 1 IPM, 2 min-max, 3 min-sum. m = ca·μ + cb·σ + cr·ref
+// per coordinate (μ, σ: mean and population standard deviation of the honest values). ALIE and IPM
+// take (ca, cb, cr) from the host: one launch, which also records z (−cb) or ε (−ca) in gamma[0].
+// min-max / min-sum: four launches (Krum's distances, the statistics a_i = |μ − x_i|²,
+// b_i = <μ − x_i, σ>, s = |σ|², one block that solves for γ, the write with cb = −γ read from device
+// memory); device outputs gamma[1] (float) and stat[2K+3] (double: a, b, s, D, S). work holds
+// fl_collude_work(n, K) floats; the grids are fl_krum_grid(n, K). ref may be null unless kind is IPM.
+inline int64_t fl_collude_work(int64_t n, int K) { return (int64_t)fl_krum_grid(n, K) * (K * (K - 1) / 2 + 2 * K + 1); }
+void fl_collude(float* work, const OutPtrs& outs, int P, const RowPtrs& rows, int K, int kind, float ca, float cb, float cr, const float* ref,
+                int64_t n, float* gamma, double* stat, hipStream_t s);
 // SCAFFOLD server step, packed buffer [Σ w_k dy_k | Σ w_k | Σ dc_k | K] (2n + 2 floats):
 //   reduce: buf <- the local contributions (before the cross-rank all-reduce)
 //   apply : out rows <- x_start + glr · buf[0:n] / buf[n];  c <- (c_init ? 0 : c) + buf[n+1:2n+1] / buf[2n+1]

@@ -878,6 +878,226 @@ __global__ __launch_bounds__(KRUM_SELECT_BLOCK) void k_gm_reweight(const float* 
     for (int k = 0; k < K; ++k) coef[k] = (float)(beta[k] / bs);
 }
 
+// Colluding omniscient attacks (ALIE: Baruch et al., 2019; IPM: Xie et al., 2019; min-max and
+// min-sum: Shejwalkar & Houmansadr, 2021): one crafted row m, computed from the K honest rows and
+// stored into the P attackers' rows. Built like Krum and the geometric median above: per-block
+// slabs, one block that sums them in double, no float atomics, no cross-block synchronisation,
+// nothing for the host to read.
+//   k_pairwise_sqdist<K>   : Krum's (min-max / min-sum only: D and S come from it)
+//   k_collude_stats<K>     : per block the 2K + 1 partial sums a_0..a_{K-1}, b_0..b_{K-1}, s of its
+//                            coordinates, stored into the block's slab of work[grid][2K+1]
+//                            (a_i = |μ − x_i|², b_i = <μ − x_i, σ>, s = |σ|²)
+//   k_collude_solve        : one block sums both kinds of slabs in a fixed order (double), takes
+//                            D = max d_ij or S = max_i Σ_j d_ij and solves for γ; writes gamma / stat
+//   k_collude_write<K>     : out rows <- m = ca·μ + cb·σ + cr·r, cb = −γ from device memory
+// ALIE and IPM take ca, cb, cr from the host and are the last launch alone.
+// There is no NaN screening: a NaN in an honest row reaches σ, γ and m.
+//
+// One coordinate, in fp32, in exactly this order (x_0..x_{K-1} the honest values):
+//   u_k = x_k − x_0                     (u_0 = 0; rows differ by ~1e-3 of their norm, see k_gm_dist)
+//   δ   = (((0 + u_0) + u_1) + … + u_{K-1}) / K
+//   e_k = u_k − δ                       (μ = x_0 + δ is never rounded to fp32)
+//   q   = fma(e_{K-1}, e_{K-1}, … fma(e_1, e_1, fma(e_0, e_0, 0)))
+//   σ   = sqrt(q / K)
+// e[] holds x on entry and e on return.
+template <int K>
+__device__ __forceinline__ void collude_coord(float (&e)[K], float& delta, float& sigma) {
+  const float x0 = e[0];
+  float sum = 0.f;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    e[k] -= x0;
+    sum += e[k];
+  }
+  delta = sum / (float)K;
+  float q = 0.f;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    e[k] -= delta;
+    q = fmaf(e[k], e[k], q);
+  }
+  sigma = sqrtf(q / (float)K);
+}
+
+// Per thread and coordinate (components x, y, z, w of a group in this order, groups in grid-stride
+// order): a_k <- fma(e_k, e_k, a_k), b_k <- fma(−e_k, σ, b_k), s <- fma(σ, σ, s). Coordinates past n
+// read as 0 in every row and add 0.
+template <int K, bool VEC>
+__global__ __launch_bounds__(FL_BLOCK) void k_collude_stats(float* __restrict__ work, RowPtrs rows, int64_t n) {
+  constexpr int W = 2 * K + 1;
+  __shared__ float part[KRUM_WAVES][W];
+  float acc[W];
+#pragma unroll
+  for (int q = 0; q < W; ++q) acc[q] = 0.f;
+  const int64_t groups = (n + 3) / 4;
+  const int64_t stride = (int64_t)gridDim.x * FL_BLOCK;
+  for (int64_t g = (int64_t)blockIdx.x * FL_BLOCK + threadIdx.x; g < groups; g += stride) {
+    float4 v[K];
+    // one decision for all K rows (see k_gm_dist)
+    if (VEC && 4 * g + 4 <= n) {
+#pragma unroll
+      for (int k = 0; k < K; ++k) v[k] = reinterpret_cast<const float4*>(rows.p[k])[g];
+    } else {
+#pragma unroll
+      for (int k = 0; k < K; ++k) v[k] = load4<false>(rows.p[k], g, n);
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      float e[K], delta, sigma;
+#pragma unroll
+      for (int k = 0; k < K; ++k) e[k] = c == 0 ? v[k].x : c == 1 ? v[k].y : c == 2 ? v[k].z : v[k].w;
+      collude_coord<K>(e, delta, sigma);
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        acc[k] = fmaf(e[k], e[k], acc[k]);
+        acc[K + k] = fmaf(-e[k], sigma, acc[K + k]);
+      }
+      acc[2 * K] = fmaf(sigma, sigma, acc[2 * K]);
+    }
+  }
+  // wave reduction (xor butterfly: a fixed order), then the block's waves through LDS in wave order
+#pragma unroll
+  for (int q = 0; q < W; ++q) {
+    float s = acc[q];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+    acc[q] = s;
+  }
+  const int wave = threadIdx.x / 64;
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int q = 0; q < W; ++q) part[wave][q] = acc[q];
+  }
+  __syncthreads();
+  if (threadIdx.x < W) {
+    float s = part[0][threadIdx.x];
+#pragma unroll
+    for (int w = 1; w < KRUM_WAVES; ++w) s += part[w][threadIdx.x];
+    work[(int64_t)blockIdx.x * W + threadIdx.x] = s;  // every block stores its whole slab
+  }
+}
+
+// One block. The pair slabs pairs[Gp][K(K-1)/2] go through krum_sum_slabs; the stats slabs
+// stats[G][2K+1] are summed in the same fixed two-level order (C = KRUM_SELECT_BLOCK / (2K+1) chunks
+// of consecutive slabs, then the chunks in chunk order). Thread 0 then works in double:
+//   D = max_ij d_ij, S = max_i Σ_j d_ij (j ascending)
+//   min-max: the largest γ >= 0 with max_i |m − x_i|² <= D, m = μ − γσ. |m − x_i|² = a_i − 2γ b_i + γ² s,
+//            so γ = min_i (b_i + sqrt(max(0, b_i² + s (D − a_i)))) / s, i ascending
+//   min-sum: Σ_i |m − x_i|² = Σ a_i + γ² K s = K s (1 + γ²) <= S, so γ = sqrt(max(0, S / (K s) − 1))
+// s = 0 (one honest row, or all equal) gives γ = 0: m = μ. gamma[0] = (float)γ;
+// stat = [a_0..a_{K-1}, b_0..b_{K-1}, s, D, S].
+#define COLLUDE_ALIE 0
+#define COLLUDE_IPM 1
+#define COLLUDE_MIN_MAX 2
+#define COLLUDE_MIN_SUM 3
+__global__ __launch_bounds__(KRUM_SELECT_BLOCK) void k_collude_solve(const float* __restrict__ pairs, int Gp, const float* __restrict__ stats, int G, int K,
+                                                                     int kind, float* __restrict__ gamma, double* __restrict__ stat) {
+  __shared__ double d[16][16];
+  __shared__ double part[KRUM_SELECT_BLOCK];
+  __shared__ double sum[33];
+  const int tid = threadIdx.x;
+  krum_sum_slabs(pairs, Gp, K, d, part);
+  const int W = 2 * K + 1;
+  const int C = KRUM_SELECT_BLOCK / W;  // W <= 33: at least 31 chunks
+  if (tid < C * W) {
+    const int p = tid % W, c = tid / W;
+    const int per = (G + C - 1) / C;
+    const int g1 = min(G, (c + 1) * per);
+    int g = c * per;
+    double s = 0.0;
+    for (; g + 8 <= g1; g += 8) {
+      float v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) v[u] = stats[(int64_t)(g + u) * W + p];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) s += (double)v[u];
+    }
+    for (; g < g1; ++g) s += (double)stats[(int64_t)g * W + p];
+    part[c * W + p] = s;
+  }
+  __syncthreads();
+  if (tid < W) {
+    double s = 0.0;
+    for (int c = 0; c < C; ++c) s += part[c * W + tid];
+    sum[tid] = s;
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  double D = 0.0, S = 0.0;
+  for (int i = 0; i < K; ++i) {
+    double row = 0.0;
+    for (int j = 0; j < K; ++j) {
+      row += d[i][j];
+      if (d[i][j] > D) D = d[i][j];
+    }
+    if (row > S) S = row;
+  }
+  const double s = sum[2 * K];
+  double g = 0.0;
+  if (s > 0.0) {
+    if (kind == COLLUDE_MIN_MAX) {
+      for (int i = 0; i < K; ++i) {
+        const double a = sum[i], b = sum[K + i];
+        const double disc = b * b + s * (D - a);
+        const double gi = (b + sqrt(disc > 0.0 ? disc : 0.0)) / s;
+        if (i == 0 || gi < g) g = gi;
+      }
+      if (g < 0.0) g = 0.0;
+    } else {
+      const double r = S / ((double)K * s) - 1.0;
+      g = sqrt(r > 0.0 ? r : 0.0);
+    }
+  }
+  gamma[0] = (float)g;
+  for (int q = 0; q < W; ++q) stat[q] = sum[q];
+  stat[W] = D;
+  stat[W + 1] = S;
+}
+
+// out rows 0..P-1 <- m. Per coordinate δ and σ as k_collude_stats computes them (collude_coord), then
+//   cb' = gamma != nullptr ? −gamma[0] : cb
+//   t   = fma(cb', σ, ca · δ)
+//   m   = fma(ca, x_0, t);  with a reference row r: m = fma(cr, r, m)
+// ALIE: (ca, cb, cr) = (1, −z, 0); IPM: (−ε, 0, 1 + ε) with r; min-max / min-sum: (1, ·, 0) and γ
+// from device memory. Every thread loads its four coordinates from all rows (and r) before it
+// stores. gamma_out != nullptr: thread 0 of the grid records gamma_val there (ALIE's z, IPM's ε).
+template <int K, bool VEC>
+__global__ __launch_bounds__(FL_BLOCK) void k_collude_write(OutPtrs outs, int P, RowPtrs rows, const float* __restrict__ ref, float ca, float cb, float cr,
+                                                            const float* __restrict__ gamma, float* __restrict__ gamma_out, float gamma_val, int64_t n) {
+  if (gamma != nullptr) cb = -gamma[0];
+  if (gamma_out != nullptr && blockIdx.x == 0 && threadIdx.x == 0) gamma_out[0] = gamma_val;
+  const int64_t groups = (n + 3) / 4;
+  const int64_t stride = (int64_t)gridDim.x * FL_BLOCK;
+  for (int64_t g = (int64_t)blockIdx.x * FL_BLOCK + threadIdx.x; g < groups; g += stride) {
+    float4 v[K];
+    float4 r4 = {0.f, 0.f, 0.f, 0.f};
+    if (VEC && 4 * g + 4 <= n) {
+#pragma unroll
+      for (int k = 0; k < K; ++k) v[k] = reinterpret_cast<const float4*>(rows.p[k])[g];
+      if (ref != nullptr) r4 = reinterpret_cast<const float4*>(ref)[g];
+    } else {
+#pragma unroll
+      for (int k = 0; k < K; ++k) v[k] = load4<false>(rows.p[k], g, n);
+      if (ref != nullptr) r4 = load4<false>(ref, g, n);
+    }
+    float o[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      float e[K], delta, sigma;
+#pragma unroll
+      for (int k = 0; k < K; ++k) e[k] = c == 0 ? v[k].x : c == 1 ? v[k].y : c == 2 ? v[k].z : v[k].w;
+      const float x0 = e[0];
+      collude_coord<K>(e, delta, sigma);
+      const float t = fmaf(cb, sigma, ca * delta);
+      float m = fmaf(ca, x0, t);
+      if (ref != nullptr) m = fmaf(cr, c == 0 ? r4.x : c == 1 ? r4.y : c == 2 ? r4.z : r4.w, m);
+      o[c] = m;
+    }
+    const float4 res = {o[0], o[1], o[2], o[3]};
+    for (int p = 0; p < P; ++p) store4<VEC>(outs.p[p], g, n, res);
+  }
+}
+
 // SCAFFOLD (Karimireddy et al.) server step in two launches around one all-reduce; float4 body,
 // scalar tail. Sums run in the same k order as the host reference.
 __global__ __launch_bounds__(FL_BLOCK) void k_scaffold_reduce(float* __restrict__ buf, RowPtrs dy, RowPtrs dc, RowW w, int K, int64_t n) {
@@ -1088,6 +1308,45 @@ void fl_geometric_median(float* work, const RowPtrs& rows, const RowW& w, int K,
     }
     hipLaunchKernelGGL(k_gm_reweight, dim3(1), dim3(KRUM_SELECT_BLOCK), 0, s, work, (int)grid, K, t < 0 ? GM_SCREEN : GM_ITERATE, t < 0 ? 0 : t, w, nu,
                        what, coef, dist, obj);
+  }
+}
+void fl_collude(float* work, const OutPtrs& outs, int P, const RowPtrs& rows, int K, int kind, float ca, float cb, float cr, const float* ref,
+                int64_t n, float* gamma, double* stat, hipStream_t s) {
+  const bool solve = kind == COLLUDE_MIN_MAX || kind == COLLUDE_MIN_SUM;
+  if (solve) {
+    const unsigned gp = launch_pairwise_sqdist(work, rows, K, n, s);
+    const unsigned grid = fl_krum_grid(n, K);
+    float* stats = work + (int64_t)grid * (K * (K - 1) / 2);
+    const bool vec = all_aligned16(rows, K, nullptr, 0);
+    const dim3 g(grid), b(FL_BLOCK);
+    switch (K) {
+#define CST_CASE(KK)                                                                      \
+  case KK:                                                                                \
+    if (vec) hipLaunchKernelGGL((k_collude_stats<KK, true>), g, b, 0, s, stats, rows, n); \
+    else hipLaunchKernelGGL((k_collude_stats<KK, false>), g, b, 0, s, stats, rows, n);    \
+    break;
+      CST_CASE(1) CST_CASE(2) CST_CASE(3) CST_CASE(4) CST_CASE(5) CST_CASE(6) CST_CASE(7) CST_CASE(8)
+      CST_CASE(9) CST_CASE(10) CST_CASE(11) CST_CASE(12) CST_CASE(13) CST_CASE(14) CST_CASE(15) CST_CASE(16)
+#undef CST_CASE
+      default: return;
+    }
+    hipLaunchKernelGGL(k_collude_solve, dim3(1), dim3(KRUM_SELECT_BLOCK), 0, s, work, (int)gp, stats, (int)grid, K, kind, gamma, stat);
+  }
+  const bool vec = all_aligned16(rows, K, &outs, P) && (reinterpret_cast<uintptr_t>(ref) & 15u) == 0;
+  const float* gin = solve ? gamma : nullptr;
+  float* gout = solve ? nullptr : gamma;
+  const float gval = kind == COLLUDE_ALIE ? -cb : -ca;
+  const dim3 g(grid_for((n + 3) / 4)), b(FL_BLOCK);
+  switch (K) {
+#define CWR_CASE(KK)                                                                                                         \
+  case KK:                                                                                                                   \
+    if (vec) hipLaunchKernelGGL((k_collude_write<KK, true>), g, b, 0, s, outs, P, rows, ref, ca, cb, cr, gin, gout, gval, n); \
+    else hipLaunchKernelGGL((k_collude_write<KK, false>), g, b, 0, s, outs, P, rows, ref, ca, cb, cr, gin, gout, gval, n);    \
+    break;
+    CWR_CASE(1) CWR_CASE(2) CWR_CASE(3) CWR_CASE(4) CWR_CASE(5) CWR_CASE(6) CWR_CASE(7) CWR_CASE(8)
+    CWR_CASE(9) CWR_CASE(10) CWR_CASE(11) CWR_CASE(12) CWR_CASE(13) CWR_CASE(14) CWR_CASE(15) CWR_CASE(16)
+#undef CWR_CASE
+    default: break;
   }
 }
 void fl_scaffold_reduce(float* buf, const RowPtrs& dy, const RowPtrs& dc, const RowW& w, int K, int64_t n, hipStream_t s) {

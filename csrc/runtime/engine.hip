@@ -1123,6 +1123,35 @@ int myfyp_geomed_multi(const uint64_t* outs, int P, const uint64_t* srcs, const 
   }
   return 0;
 }
+// Floats of the workspace of myfyp_collude_multi for n coordinates of K honest rows.
+int64_t myfyp_collude_work(int64_t n, int K) { return fl_collude_work(n, K); }
+// Colluding attack: out rows 0..P-1 <- the crafted row m of the K honest rows (kind 0 ALIE, 1 IPM,
+// 2 min-max, 3 min-sum; m = ca·μ + cb·σ + cr·ref, cb = −γ solved on the device for kinds 2 and 3).
+// Device outputs gamma[1] (float) and, for kinds 2 and 3, stat[2K+3] (double). Enqueues only: one
+// launch for ALIE / IPM, four for min-max / min-sum.
+int myfyp_collude_multi(const uint64_t* outs, int P, const uint64_t* srcs, int K, int kind, float ca, float cb, float cr, const float* ref, int64_t n,
+                        float* work, float* gamma, double* stat, void* stream) {
+  if (!rows_ok(K, "collude") || !rows_ok(P, "collude outputs")) return 2;
+  if (kind < 0 || kind > 3) {
+    g_last_error = "collude: kind is 0 (alie), 1 (ipm), 2 (min_max) or 3 (min_sum)";
+    return 2;
+  }
+  if (kind == 1 && ref == nullptr) {
+    g_last_error = "collude: ipm needs the reference row";
+    return 2;
+  }
+  if (n < 1 || srcs == nullptr || outs == nullptr || gamma == nullptr || (kind >= 2 && (work == nullptr || stat == nullptr))) {
+    g_last_error = "collude: n >= 1 and the row tables and the work / gamma / stat buffers are required";
+    return 2;
+  }
+  RowPtrs rows{};
+  OutPtrs o{};
+  for (int k = 0; k < K; ++k) rows.p[k] = reinterpret_cast<const float*>(srcs[k]);
+  for (int p = 0; p < P; ++p) o.p[p] = reinterpret_cast<float*>(outs[p]);
+  fl_collude(work, o, P, rows, K, kind, ca, cb, cr, ref, n, gamma, stat, (hipStream_t)stream);
+  CHECK_HIP(hipGetLastError());
+  return 0;
+}
 int myfyp_scaffold_reduce(float* buf, const uint64_t* dy, const uint64_t* dc, const float* w, int K, int64_t n, void* stream) {
   if (K < 0 || K > 16) {
     g_last_error = "scaffold_reduce supports 0..16 rows";

@@ -41,10 +41,17 @@ def final(logs: dict, key: str):
     return vals[-1][1] if vals else "N/A"
 
 
-def main(seed: int = 666, n: int = 3, r: int = 1, attack: str = "sign_flip", node: int = 0, sigma: float = 0.1, protocol: str = "memory") -> dict:
+COLLUDING = ("alie", "ipm", "min_max", "min_sum")  # fault_injection.ColludingAttack: collective protocol only
+
+
+def main(seed: int = 666, n: int = 3, r: int = 1, attack: str = "sign_flip", node: int = 0, sigma: float = 0.1, protocol: str = "memory",
+         attack_nodes=None) -> dict:
     set_test_settings()
     normal = run_experiment(config(f"fyp-normal-{seed}", seed, n, r, protocol=protocol), verbose=False)
-    att = {"node": node, "kind": attack, "sigma": sigma}
+    if attack in COLLUDING:  # the attackers see the honest models of the round and send one crafted row
+        att = {"kind": attack, "nodes": list(attack_nodes) if attack_nodes else [node]}
+    else:
+        att = {"node": node, "kind": attack, "sigma": sigma}
     attacked = run_experiment(config(f"fyp-{attack}-{seed}", seed, n, r, attack=att, protocol=protocol), verbose=False)
     print(f"{'Metric':<14} | {'Normal Experiment':<32} | {'Attack Experiment (' + attack + ')':<32}")
     print("-" * 84)
@@ -58,9 +65,10 @@ if __name__ == "__main__":
     ap.add_argument("--seed", type=int, default=666)
     ap.add_argument("--nodes", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=1)
-    ap.add_argument("--attack", choices=["sign_flip", "gaussian_noise"], default="sign_flip")
+    ap.add_argument("--attack", choices=["sign_flip", "gaussian_noise", *COLLUDING], default="sign_flip")
     ap.add_argument("--attack_node", type=int, default=0)
+    ap.add_argument("--attack_nodes", type=int, nargs="+", default=None, help="the colluding attackers (alie / ipm / min_max / min_sum; --protocol collective)")
     ap.add_argument("--sigma", type=float, default=0.1)
     ap.add_argument("--protocol", default="memory", choices=["memory", "grpc", "collective"])
     a = ap.parse_args()
-    main(a.seed, a.nodes, a.rounds, a.attack, a.attack_node, a.sigma, a.protocol)
+    main(a.seed, a.nodes, a.rounds, a.attack, a.attack_node, a.sigma, a.protocol, a.attack_nodes)

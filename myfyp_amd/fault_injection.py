@@ -27,6 +27,7 @@ from myfyp_amd import ops
 from myfyp_amd.management.logger import logger
 
 ATTACKS = ("sign_flip", "gaussian_noise", "scale")
+COLLUDING = ("alie", "ipm", "min_max", "min_sum")  # ColludingAttack: the attackers see the honest models
 
 
 def _learner(target):
@@ -92,6 +93,66 @@ class ModelPoisoning:
 
     def remove(self) -> None:
         self.learner.fit = self._orig_fit  # type: ignore[method-assign]
+
+
+class ColludingAttack:
+    """Omniscient, colluding attackers on the collective protocol: between the local epoch and the
+    round's aggregation every attacker that trained receives one crafted row, computed on the device
+    from the honest trainers' rows of the round (``weights_plane.collude`` / ``ops.collude_into``):
+
+    * ``alie``    — μ − z·σ per coordinate (Baruch et al., 2019); ``z`` defaults to ``ops.alie_z``
+    * ``ipm``     — the round's start model minus ``eps`` times the honest mean update (Xie et al., 2019)
+    * ``min_max`` / ``min_sum`` — μ − γ·σ with the largest γ that keeps the row no farther from the
+      honest rows than they are from each other (Shejwalkar & Houmansadr, 2021)
+
+    ``nodes_or_fed`` is the :class:`Federation` or any of its nodes (a list of them too);
+    ``attackers`` are nodes or addresses, on any rank: every rank installs the same attack. It hooks
+    ``Federation.pre_aggregation_hooks``, which all three round paths call, so it works where
+    :class:`ModelPoisoning` (a wrapper of ``learner.fit``) is never reached. After a round ``last``
+    is ``(honest addresses in row order, attacker addresses, gamma, stat)``; ``gamma`` and ``stat``
+    are device tensors and reading them is the caller's synchronisation. ``rounds`` counts the
+    hook's calls."""
+
+    def __init__(self, nodes_or_fed, attackers, kind: str = "min_max", z: Optional[float] = None, eps: float = 0.5) -> None:
+        from myfyp_amd.parallel.federation import Federation
+
+        if kind not in COLLUDING:
+            raise ValueError(f"unknown colluding attack {kind!r}; choose from {COLLUDING}")
+        self.fed = nodes_or_fed if isinstance(nodes_or_fed, Federation) else Federation.get()
+        self.attackers = [getattr(a, "addr", a) for a in attackers]
+        if not self.attackers:
+            raise ValueError("a colluding attack needs at least one attacker")
+        self.kind, self.z, self.eps = kind, z, float(eps)
+        self.last = None
+        self.rounds = 0
+        self._refs: Dict[str, torch.Tensor] = {}
+        if kind == "ipm":
+            aggs = [getattr(n.aggregator, "collective_kind", None) for n in self.fed.local_nodes.values()]
+            if "neighbor" in aggs:
+                raise ValueError("ipm needs every peer to start a round from one model: NeighborAvg (collective_kind 'neighbor') leaves them different")
+            self.fed.round_start_hooks.append(self._round_start)
+        self.fed.pre_aggregation_hooks.append(self._hook)
+
+    def _round_start(self, round_: int, fed) -> None:
+        from myfyp_amd.parallel import weights_plane
+
+        self._refs = weights_plane.collude_snapshot(fed, set(self.attackers))
+
+    def _hook(self, round_: int, fed, weights: Dict[str, float]) -> None:
+        from myfyp_amd.parallel import weights_plane
+
+        self.rounds += 1
+        res = weights_plane.collude(fed, weights, self.attackers, self.kind, z=self.z, eps=self.eps, refs=self._refs)
+        if res is not None:
+            self.last = res
+            logger.debug(f"rank{fed.rank}", f"☠️ colluding attack {self.kind}: {len(res[1])} attackers hide among {len(res[0])} honest trainers (round {round_})")
+
+    def remove(self) -> None:
+        for hooks, fn in ((self.fed.pre_aggregation_hooks, self._hook), (self.fed.round_start_hooks, self._round_start)):
+            try:
+                hooks.remove(fn)
+            except ValueError:
+                pass
 
 
 class StageFault:

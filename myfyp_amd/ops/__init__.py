@@ -22,6 +22,9 @@ Ops
 * ``adam_step`` / ``sgd_step`` — fused optimizers over a flat buffer, optionally with the FedProx
   proximal term and the SCAFFOLD control-variate correction fused in (K5, K8, K13)
 * ``scale_add_noise`` — attack injection (sign flip / Gaussian noise, K14)
+* ``collude_into`` — colluding omniscient attacks (ALIE, IPM, min-max, min-sum, K14): one crafted
+  row from the honest rows' mean and spread written into the attackers' rows, γ solved on the
+  device (≤ 16 honest rows); returns ``(gamma, stat)``
 """
 
 from __future__ import annotations
@@ -42,6 +45,8 @@ __all__ = [
     "krum_into",
     "geometric_median_into",
     "bulyan_into",
+    "collude_into",
+    "alie_z",
     "adam_step",
     "sgd_step",
     "scale_add_noise",
@@ -481,6 +486,106 @@ def geometric_median_into(rows: Sequence[torch.Tensor], outs: Sequence[torch.Ten
         for o in outs:
             o.copy_(mean)
     return coef.to(dev), dist.to(dev), obj.to(dev)
+
+
+COLLUDE_KINDS = ("alie", "ipm", "min_max", "min_sum")
+
+
+def alie_z(k: int, f: int) -> float:
+    """ALIE's default z for ``k`` peers of which ``f`` attack (Baruch et al., 2019):
+    ``Φ⁻¹((k − f − s) / (k − f))`` with ``s = ⌊k/2 + 1⌋ − f`` the honest peers the attackers must
+    win over; 0 where that fraction is not inside (0, 1)."""
+    from statistics import NormalDist
+
+    k, f = int(k), int(f)
+    s = k // 2 + 1 - f
+    if k - f <= 0:
+        return 0.0
+    p = (k - f - s) / (k - f)
+    return float(NormalDist().inv_cdf(p)) if 0.0 < p < 1.0 else 0.0
+
+
+def collude_into(rows: Sequence[torch.Tensor], outs: Sequence[torch.Tensor], kind: str, z: Optional[float] = None, eps: float = 0.5,
+                 ref: Optional[torch.Tensor] = None):
+    """A colluding, omniscient attack: the crafted row ``m`` of the honest 1-D fp32 ``rows``, stored
+    into every one of ``outs`` (the attackers' rows). With μ and σ the per-coordinate mean and
+    population standard deviation of the H honest values:
+
+    * ``alie``    — ``m = μ − z·σ``; ``z`` defaults to :func:`alie_z` of ``(H + len(outs), len(outs))``
+    * ``ipm``     — ``m = ref − eps·(μ − ref)``, ``ref`` the model the round started from
+    * ``min_max`` — ``m = μ − γ·σ`` with the largest γ >= 0 for which ``max_i ‖m − x_i‖² <= D``,
+      ``D = max_ij ‖x_i − x_j‖²``: ``γ = min_i (b_i + sqrt(max(0, b_i² + s·(D − a_i)))) / s``
+    * ``min_sum`` — the same with ``Σ_i ‖m − x_i‖² <= S``, ``S = max_i Σ_j ‖x_i − x_j‖²``:
+      ``γ = sqrt(max(0, S/(H·s) − 1))``
+
+    where ``a_i = ‖μ − x_i‖²``, ``b_i = ⟨μ − x_i, σ⟩`` and ``s = ‖σ‖²``; ``s = 0`` gives γ = 0. There
+    is no NaN screening. Returns ``(gamma [1] float32: γ, ALIE's z or IPM's eps; stat [2H + 3]
+    float64: a, b, s, D, S for min_max / min_sum, zeros otherwise)`` on the rows' device.
+
+    On the GPU (H <= 16 rows, <= 16 outputs) it is one launch for ``alie`` / ``ipm``
+    (``k_collude_write<H>``) and four for ``min_max`` / ``min_sum`` (``k_pairwise_sqdist<H>``,
+    ``k_collude_stats<H>``, ``k_collude_solve``, ``k_collude_write<H>``) that only enqueue: γ never
+    leaves the device. Elsewhere: float64 torch math (the oracle)."""
+    if kind not in COLLUDE_KINDS:
+        raise ValueError(f"unknown colluding attack {kind!r}; choose from {COLLUDE_KINDS}")
+    h = len(rows)
+    if h < 1:
+        raise ValueError("a colluding attack needs at least one honest row")
+    if not outs:
+        raise ValueError("a colluding attack needs at least one output row")
+    if kind == "ipm" and ref is None:
+        raise ValueError("ipm needs ref, the model the round started from")
+    n = rows[0].numel()
+    if n < 1 or any(t.numel() != n for t in [*rows, *outs]) or (ref is not None and ref.numel() != n):
+        raise ValueError("colluding attack: rows, outputs and ref must share one length >= 1")
+    row_ptrs = {t.data_ptr() for t in rows}
+    if any(o.data_ptr() in row_ptrs for o in outs):
+        raise ValueError("colluding attack: an output is also an honest row")
+    dev = rows[0].device
+    zz = float(alie_z(h + len(outs), len(outs)) if z is None else z)
+    eps = float(eps)
+    ca, cb, cr = {"alie": (1.0, -zz, 0.0), "ipm": (-eps, 0.0, 1.0 + eps)}.get(kind, (1.0, 0.0, 0.0))
+    if _native_rows(rows, outs) and (ref is None or (ref.device == dev and ref.is_contiguous() and ref.dtype == torch.float32)):
+        lib = _lib()
+        solve = kind in ("min_max", "min_sum")
+        work = torch.empty(max(1, int(lib.myfyp_collude_work(n, h))), dtype=torch.float32, device=dev) if solve else None
+        gamma = torch.empty(1, dtype=torch.float32, device=dev)
+        stat = torch.empty(2 * h + 3, dtype=torch.float64, device=dev) if solve else torch.zeros(2 * h + 3, dtype=torch.float64, device=dev)
+        src, keep_s = _host_ptrs(rows)
+        dst, keep_d = _host_ptrs(outs)
+        _native.check(lib.myfyp_collude_multi(dst, len(outs), src, h, COLLUDE_KINDS.index(kind), ca, cb, cr, _ptr(ref if kind == "ipm" else None), n,
+                                              _ptr(work), gamma.data_ptr(), stat.data_ptr(), _stream()), "collude_multi")
+        return gamma, stat
+    x = torch.stack([r.detach().double().reshape(-1) for r in rows])
+    mu = x.mean(dim=0)
+    sigma = ((x - mu).square().sum(dim=0) / h).sqrt()
+    stat = torch.zeros(2 * h + 3, dtype=torch.float64)
+    if kind == "alie":
+        g, m = zz, mu - zz * sigma
+    elif kind == "ipm":
+        r = ref.detach().double().reshape(-1)
+        g, m = eps, r - eps * (mu - r)
+    else:
+        a = (mu - x).square().sum(dim=1)
+        b = ((mu - x) * sigma).sum(dim=1)
+        s = float(sigma.square().sum())
+        d = torch.zeros(h, h, dtype=torch.float64)
+        for i in range(h):
+            for j in range(i + 1, h):
+                d[i, j] = d[j, i] = float((x[i] - x[j]).square().sum())
+        big_d, big_s = float(d.max()), float(d.sum(dim=1).max())
+        g = 0.0
+        if s > 0:
+            if kind == "min_max":
+                g = max(0.0, min((float(b[i]) + max(0.0, float(b[i]) ** 2 + s * (big_d - float(a[i]))) ** 0.5) / s for i in range(h)))
+            else:
+                g = max(0.0, big_s / (h * s) - 1.0) ** 0.5
+        m = mu - g * sigma
+        stat[:h], stat[h : 2 * h], stat[2 * h], stat[2 * h + 1], stat[2 * h + 2] = a.cpu(), b.cpu(), s, big_d, big_s
+    with torch.no_grad():
+        for o in outs:
+            o.copy_(m.view_as(o))
+    return torch.tensor([g], dtype=torch.float32, device=dev), stat.to(dev)
 
 
 def scaffold_reduce(buf: torch.Tensor, dys: Sequence[torch.Tensor], dcs: Sequence[torch.Tensor], weights: Sequence[float]) -> None:

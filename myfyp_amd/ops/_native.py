@@ -47,6 +47,8 @@ _SIGNATURES = {
     "myfyp_bulyan_mean_multi": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p]),
     "myfyp_geomed_work": (c_int64, [c_int64, c_int]),
     "myfyp_geomed_multi": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, ctypes.c_double, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "myfyp_collude_work": (c_int64, [c_int64, c_int]),
+    "myfyp_collude_multi": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_float, c_float, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "myfyp_scaffold_reduce": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
     "myfyp_scaffold_apply": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_float, c_int64, c_void_p]),
     # optimizers over flat buffers

@@ -301,6 +301,10 @@ class Federation:
         # called once per round and process when the round's train set is known, before its first
         # launch (the vote's gang leader, or the round driver): (round, federation)
         self.round_start_hooks: List[Callable[[int, "Federation"], None]] = []
+        # called once per round and process by the aggregation's gang leader (or the round driver)
+        # immediately before the round's aggregation, after the local epochs are enqueued:
+        # (round, federation, {local addr: sample weight, 0 for a non-trainer})
+        self.pre_aggregation_hooks: List[Callable[[int, "Federation", Dict[str, float]], None]] = []
         self.stats: Dict[str, List[float]] = {}
         self._lock = make_lock("Federation.state")
         self._cpu_pg = None

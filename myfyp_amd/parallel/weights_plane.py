@@ -1143,6 +1143,161 @@ def _mesh_robust(fed: Federation, arrived: Dict[str, Tuple[float, Any]], aggrega
             _publish_selection(fed, [a for a, _ in ranks[r]], aggregator, order, coef)
 
 
+# ---------------------------------------------------------------------------------------------
+# colluding attacks (fault_injection.ColludingAttack): ALIE, IPM, min-max, min-sum
+# ---------------------------------------------------------------------------------------------
+@traced("collude")
+def collude(fed: Federation, weights: Dict[str, float], attackers, kind: str, z: Optional[float] = None, eps: float = 0.5,
+            refs: Optional[Dict[str, torch.Tensor]] = None):
+    """Rewrite the attackers' rows in place, on the device, between the local epoch and the round's
+    aggregation (a ``Federation.pre_aggregation_hooks`` entry calls this with its ``weights``: the
+    local peers' sample weights, 0 for a non-trainer). The attackers are omniscient and collude:
+    all of them that trained this round receive the one row ``ops.collude_into`` crafts from the
+    honest trainers' rows (the trainers that are not attackers), in the row order of ``_robust``:
+    rank first, then local order. Laid out as ``_robust`` / ``_mesh_robust``: one rank reads the live
+    rows and writes the local attackers' rows directly; several ranks gather order and counts (one
+    ``all_gather_object``) and the honest rows (one ``all_gather_into_tensor_``), and every rank
+    computes the same row, γ included bit for bit, and writes its own attackers; a mesh gathers once
+    and computes per device. An attacker that did not train this round is left alone; with no honest
+    trainer or no attacking trainer nothing happens, on every rank. The launches go to the current
+    stream of the rows' device: behind the epoch the gang leader enqueued, ahead of the aggregation.
+
+    ``refs`` (IPM): ``{addr: row}`` snapshots from :func:`collude_snapshot`, the model the round
+    started from. Returns ``(honest addresses in row order, attacker addresses, gamma, stat)`` with
+    the device tensors of ``ops.collude_into`` (reading them is the caller's synchronisation), or
+    None when nothing happened."""
+    attackers = set(attackers)
+    return fed.run_aggregation(lambda: _collude(fed, weights, attackers, kind, z, eps, refs or {}))
+
+
+def collude_snapshot(fed: Federation, attackers) -> Dict[str, torch.Tensor]:
+    """Device copies of the rows of the local ``attackers`` (one per device), in the layout
+    :func:`collude` reads: taken at a round's start they are IPM's reference model."""
+    local = [a for a in fed.local_order if a in fed.local_nodes]
+    learners = [fed.local_nodes[a].learner for a in local]
+    if not learners:
+        return {}
+    _, row_of = _row_fns(learners, "krum")
+    out: Dict[str, torch.Tensor] = {}
+    seen = set()
+    for a, lr in zip(local, learners):
+        if a not in attackers:
+            continue
+        key = mesh_rank_of(lr) if fed.mesh is not None else 0
+        if key in seen:
+            continue
+        seen.add(key)
+        dev = lr.flat_params().device
+        with on_device(dev), torch.no_grad():
+            out[a] = row_of(lr).detach().clone()
+    return out
+
+
+def _collude_ref(refs: Dict[str, torch.Tensor], dev: torch.device) -> Optional[torch.Tensor]:
+    for t in refs.values():
+        if t.device == dev:
+            return t
+    for t in refs.values():  # a device without an attacker of its own: a copy of another's snapshot
+        return t.to(dev)
+    return None
+
+
+def _collude_write(kind: str, rows, targets, live: bool, z, eps, ref, n_attackers: int):
+    """``ops.collude_into`` from ``rows`` into the ``targets`` learners (a scratch row when this rank
+    or device hosts no attacker: it still publishes γ). ALIE's default z counts every attacker."""
+    if kind == "alie" and z is None:
+        z = ops.alie_z(len(rows) + n_attackers, n_attackers)
+    with torch.no_grad():
+        if kind == "ipm" and ref is None:  # nothing to write here, and no reference to compute from
+            return torch.tensor([float(eps)], dtype=torch.float32, device=rows[0].device), torch.zeros(2 * len(rows) + 3, dtype=torch.float64, device=rows[0].device)
+        if live and targets:
+            return ops.collude_into(rows, [lr.flat_params() for lr in targets], kind, z=z, eps=eps, ref=ref)
+        res = torch.empty_like(rows[0])
+        out = ops.collude_into(rows, [res], kind, z=z, eps=eps, ref=ref)
+        for lr in targets:
+            _unpack_into(lr, res)
+        return out
+
+
+def _collude(fed: Federation, weights: Dict[str, float], attackers: set, kind: str, z, eps, refs):
+    if kind not in ops.COLLUDE_KINDS:
+        raise ValueError(f"unknown colluding attack {kind!r}; choose from {ops.COLLUDE_KINDS}")
+    if fed.mesh is not None:
+        return _mesh_collude(fed, weights, attackers, kind, z, eps, refs)
+    addrs = [a for a in weights if a in fed.local_nodes]
+    learners = {a: fed.local_nodes[a].learner for a in addrs}
+    trainers = [a for a in addrs if float(weights[a]) > 0]
+    honest = [a for a in trainers if a not in attackers]
+    mine = [a for a in trainers if a in attackers]
+    # every rank learns H, the row order (rank, then local order) and who attacks this round
+    gathered = fed.all_gather_object((honest, mine))
+    counts = [len(h) for h, _ in gathered]
+    order = [a for h, _ in gathered for a in h]
+    attacking = [a for _, m in gathered for a in m]
+    if not order or not attacking:
+        return None
+    live, row_of = _row_fns(list(learners.values()), "krum")
+    targets = [learners[a] for a in mine]
+    if fed.solo:  # every honest trainer is local: straight from the live rows
+        rows = [row_of(learners[a]) for a in honest]
+        dev = rows[0].device
+        with on_device(dev):
+            gamma, stat = _collude_write(kind, rows, targets, live, z, eps, _collude_ref(refs, dev), len(attacking))
+        return order, attacking, gamma, stat
+    kmax = max(1, max(counts))
+    ref_row = row_of(learners[addrs[0]])
+    n, dev = ref_row.numel(), ref_row.device
+    send = torch.zeros(kmax, n, dtype=torch.float32, device=dev)
+    for i, a in enumerate(honest):
+        send[i].copy_(row_of(learners[a]))
+    recv = torch.empty(len(counts) * kmax, n, dtype=torch.float32, device=dev)
+    fed.all_gather_into_tensor_(recv, send)
+    rows = [recv[r * kmax + i] for r, c in enumerate(counts) for i in range(c)]
+    with on_device(dev):
+        gamma, stat = _collude_write(kind, rows, targets, live, z, eps, _collude_ref(refs, dev), len(attacking))
+    return order, attacking, gamma, stat
+
+
+def _mesh_collude(fed: Federation, weights: Dict[str, float], attackers: set, kind: str, z, eps, refs):
+    """:func:`collude` over a device mesh, in the manner of ``_mesh_robust``: every device packs its
+    honest trainers' rows ([k_max, n], zero-padded), ONE mesh all-gather, then per device the crafted
+    row into a result vector unpacked into its attackers. Returns the first device's tensors."""
+    addrs = [a for a in weights if a in fed.local_nodes]
+    learners = [fed.local_nodes[a].learner for a in addrs]
+    ranks = _by_mesh_rank(fed, addrs, learners)
+    trainers = {r: [(a, lr) for a, lr in v if float(weights[a]) > 0] for r, v in ranks.items()}
+    honest = {r: [(a, lr) for a, lr in v if a not in attackers] for r, v in trainers.items()}
+    mine = {r: [(a, lr) for a, lr in v if a in attackers] for r, v in trainers.items()}
+    counts = [len(honest[r]) for r in fed.mesh_members]
+    order = [a for r in fed.mesh_members for a, _ in honest[r]]
+    attacking = [a for r in fed.mesh_members for a, _ in mine[r]]
+    if not order or not attacking:
+        return None
+    _, row_of = _row_fns(learners, "krum")
+    kmax = max(counts)
+    n = row_of(learners[0]).numel()
+    sends, recvs = [], []
+    for r in fed.mesh_members:
+        dev = fed.devices[r]
+        with on_device(dev):
+            s_ = torch.zeros(kmax, n, dtype=torch.float32, device=dev)
+            for i, (a, lr) in enumerate(honest[r]):
+                s_[i].copy_(row_of(lr))
+            sends.append(s_)
+            recvs.append(torch.empty(len(counts) * kmax, n, dtype=torch.float32, device=dev))
+    fed.mesh.all_gather_(recvs, sends)
+    fed.mesh_track("collude all_gather")
+    first = None
+    for r, recv in zip(fed.mesh_members, recvs):
+        if not ranks[r]:
+            continue
+        with on_device(fed.devices[r]):
+            rows = [recv[q * kmax + i] for q, c in enumerate(counts) for i in range(c)]
+            res = _collude_write(kind, rows, [lr for _, lr in mine[r]], False, z, eps, _collude_ref(refs, recv.device), len(attacking))
+            first = first or res
+    return order, attacking, first[0], first[1]
+
+
 def aggregate_generic(fed: Federation, arrived: Dict[str, Tuple[float, Any]], aggregator) -> Any:
     """Any aggregator: all-gather the trainers' wire models and reduce identically on every rank."""
     return fed.run_aggregation(lambda: _generic(fed, arrived, aggregator))

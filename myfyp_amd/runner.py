@@ -27,6 +27,8 @@ One description drives every experiment the examples, the CLI and the FYP harnes
         name: FedAvg            # FedAvg | FedMedian | Scaffold | FedProx | Krum | TrimmedMean | GeometricMedian | Bulyan
         params: {}
       attack: {node: 1, kind: sign_flip, sigma: 0.1, persistent: false}
+      # or colluding attackers (collective protocol only): {kind: min_max, nodes: [1, 5], z: 1.0, eps: 0.5}
+      # with kind alie | ipm | min_max | min_sum (fault_injection.ColludingAttack)
       faults: [{node: 2, kill_at: TrainStage, round: 1}]
       checkpoint: {dir: ckpt, every: 1, resume: false}
     network:
@@ -229,6 +231,7 @@ def run_experiment(cfg: Any, verbose: bool = True) -> Dict[str, Any]:
     nodes: List[Any] = []
     by_index: Dict[int, Any] = {}
     start_round = 0
+    colluding = None
     t_start = time.time()
     # one process per GPU (torchrun): rank r builds the contiguous block of peers it owns
     world, rank = (fed.world, fed.rank) if fed is not None else (1, 0)
@@ -244,7 +247,19 @@ def run_experiment(cfg: Any, verbose: bool = True) -> Dict[str, Any]:
             metas = [ckpt.restore_node(nd, directory=ck["dir"], exp_name=name) for nd in nodes]
             start_round = min(int(m.get("round", 0)) for m in metas)
         att = exp.get("attack")
-        if att and int(att.get("node", 0)) in by_index:
+        if att and "nodes" in att and att.get("kind") in fault_injection.COLLUDING:
+            # colluding attackers (fault_injection.ColludingAttack): every rank installs the same attack
+            if not collective:
+                raise ValueError(f"attack {att['kind']!r} with 'nodes' is a colluding attack: it needs the collective protocol, not {proto_key!r}")
+            bad = [i for i in att["nodes"] if not 0 <= int(i) < n]
+            if bad or not att["nodes"]:
+                raise ValueError(f"attack.nodes must name peers in 0..{n - 1}, got {att['nodes']}")
+            z = att.get("z")
+            colluding = fault_injection.ColludingAttack(fed, [_address(proto_key, int(i), name) for i in att["nodes"]], att["kind"],
+                                            z=None if z is None else float(z), eps=float(att.get("eps", 0.5)))
+        elif att and "nodes" in att:
+            raise ValueError(f"attack.nodes needs a colluding kind {fault_injection.COLLUDING}, got {att.get('kind')!r}")
+        elif att and int(att.get("node", 0)) in by_index:
             victim = by_index[int(att.get("node", 0))]
             if att.get("persistent"):
                 fault_injection.ModelPoisoning(victim, att.get("kind", "sign_flip"), float(att.get("sigma", 0.1)), float(att.get("factor", -1.0)), int(att.get("seed", 0)))
@@ -282,10 +297,14 @@ def run_experiment(cfg: Any, verbose: bool = True) -> Dict[str, Any]:
             "rank": rank,
             "world": world,
         }
+        if colluding is not None:
+            res["attack"] = colluding  # .last: the last round's (honest, attackers, gamma, stat); .rounds
         if verbose and rank == 0:
             print(format_results(res))
         return res
     finally:
+        if colluding is not None:
+            colluding.remove()
         for nd in nodes:
             nd.stop()
         if fed is not None:

@@ -154,6 +154,8 @@ class RoundDriver:
             mark("driver:aggregate")
             total = next(iter(states.values())).total_rounds
             aggregator = next(iter(cur.values())).kw["aggregator"]
+            for hook in list(f.pre_aggregation_hooks):
+                hook(round_, f, {a: float(n.get(a, 0)) for a in cur})
             fused_round.aggregate(f, {a: (n.get(a, 0), None) for a in cur}, aggregator, final=total is None or round_ + 1 >= total)
             for hook in list(f.round_hooks):
                 hook(round_, f)

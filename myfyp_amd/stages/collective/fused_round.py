@@ -93,6 +93,8 @@ def join(state, learner, aggregator, trainer: bool) -> None:
         if trainers:
             out = run_groups(f, trainers, lambda a: f.local_nodes[a].learner._engine.slot, lambda a: f.local_nodes[a].learner._engine.group,
                              {a: arrived[a][2] for a in trainers}, {a for a in trainers if arrived[a][3]})
+        for hook in list(f.pre_aggregation_hooks):
+            hook(round_, f, {a: float(arrived[a][1]) for a in addrs})
         aggregate(f, {a: (arrived[a][1], None) for a in addrs}, aggregator, final)
         for hook in list(f.round_hooks):
             hook(round_, f)

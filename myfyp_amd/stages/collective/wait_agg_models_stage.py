@@ -25,6 +25,8 @@ def join_aggregation(state, learner, aggregator, trainer: bool) -> None:
     final = state.total_rounds is None or round_ + 1 >= state.total_rounds
 
     def leader(arrived):
+        for hook in list(f.pre_aggregation_hooks):
+            hook(round_, f, {a: float(arrived[a][0]) for a in arrived if a in f.local_nodes})
         device_path = kind in _VOTED_KINDS and _agree_device_path(f, kind, arrived)
         if kind in _VOTED_KINDS and not device_path:
             arrived = _with_wire_models(f, arrived)
