@@ -72,3 +72,14 @@ void mlp_launch_eval_chunk(const MLPArgs& a, int base, hipStream_t s);
 void mlp_launch_sync_shadow(const MLPArgs& a, hipStream_t s);
 // max_wgs > 0 caps the grid (at least one workgroup per peer); rows are grid-strided
 void mlp_launch_gather_epoch(const MLPArgs& a, hipStream_t s, int max_wgs = 0);
+
+// direct-drive entry points for the oracle tests: each forwards a caller-built MLPArgs to the
+// launcher above and returns 1 if the launch was rejected (mlp_fused.hip)
+extern "C" {
+int mlp_debug_args_size();
+int mlp_debug_args_abi(long long* out);  // sizeof + a few offsets, guarding the ctypes mirror; returns the count
+int mlp_debug_gather_epoch(const MLPArgs* a, int max_wgs, void* stream);
+int mlp_debug_sync_shadow(const MLPArgs* a, void* stream);
+int mlp_debug_train_step(const MLPArgs* a, int step, void* stream);
+int mlp_debug_eval_chunk(const MLPArgs* a, int base, void* stream);
+}

@@ -376,10 +376,23 @@ __global__ __launch_bounds__(256) void mlp_head(MLPArgs a, int step, int base) {
 // ---------------------------------------------------------------------------------------------
 // K3: weight gradients + optimizer. grid = (nb_w1 + nb_w2 + 1, 1, P), block = 256.
 // ---------------------------------------------------------------------------------------------
+// Adam's bias corrections 1 - beta^t, formed in double from the float betas and rounded once, as the
+// flat optimizer's launcher does on the host (fl_ops.hip): in float, 1 - __powf(beta2, t) keeps only
+// ~15 bits at small t (beta2^t is within 1e-3 of 1), which put the whole update off by up to 4 of
+// its error bounds at t = 2. t is an integer and uniform per peer: a few double products by squaring.
+__device__ __forceinline__ double pow_int(double b, int t) {
+  double r = 1.0;
+  for (; t > 0; t >>= 1, b *= b)
+    if (t & 1) r *= b;
+  return r;
+}
+
 __device__ __forceinline__ void step_bias_corr(const MLPArgs& a, const int4& ctl, int step, float& bc1, float& bc2s) {
+  bc1 = bc2s = 1.f;
+  if (a.opt.kind != 0) return;  // SGD reads neither
   const int t = ctl.z + step + 1;
-  bc1 = 1.f - __powf(a.opt.beta1, (float)t);
-  bc2s = sqrtf(1.f - __powf(a.opt.beta2, (float)t));
+  bc1 = (float)(1.0 - pow_int((double)a.opt.beta1, t));
+  bc2s = (float)sqrt(1.0 - pow_int((double)a.opt.beta2, t));
 }
 
 __device__ __forceinline__ void update_elem(const MLPArgs& a, int64_t idx, float g, float bc1, float bc2s) {
@@ -788,3 +801,54 @@ extern "C" int myfyp_warm_mlp_fused() {
   hipFuncAttributes attr;
   return hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&mlp_wgrad_opt)) == hipSuccess ? 0 : 1;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Direct-drive entry points for the oracle tests (tests/test_mlp_fused_gpu.py): each launches the
+// step-path kernels above on a caller-built MLPArgs and returns 1 if the launch was rejected. The
+// persistent epoch kernels have none: their gangs spin on flags and are reached through the
+// engine only.
+// ---------------------------------------------------------------------------------------------
+extern "C" {
+
+int mlp_debug_args_size() { return (int)sizeof(MLPArgs); }
+
+int mlp_debug_args_abi(long long* out) {
+  out[0] = (long long)sizeof(MLPArgs);
+  out[1] = (long long)offsetof(MLPArgs, params);
+  out[2] = (long long)offsetof(MLPArgs, perm_stride);
+  out[3] = (long long)offsetof(MLPArgs, flags_per_peer);
+  out[4] = (long long)offsetof(MLPArgs, ctl);
+  out[5] = (long long)offsetof(MLPArgs, h1_rows);
+  out[6] = (long long)offsetof(MLPArgs, B);
+  out[7] = (long long)offsetof(MLPArgs, opt);
+  out[8] = (long long)offsetof(MLPArgs, f32_variant);
+  out[9] = (long long)sizeof(OptParams);
+  return 10;
+}
+
+int mlp_debug_gather_epoch(const MLPArgs* a, int max_wgs, void* stream) {
+  if (a == nullptr || a->P <= 0) return 1;
+  mlp_launch_gather_epoch(*a, (hipStream_t)stream, max_wgs);
+  return hipGetLastError() != hipSuccess;
+}
+
+int mlp_debug_sync_shadow(const MLPArgs* a, void* stream) {
+  if (a == nullptr || a->P <= 0) return 1;
+  mlp_launch_sync_shadow(*a, (hipStream_t)stream);
+  return hipGetLastError() != hipSuccess;
+}
+
+int mlp_debug_train_step(const MLPArgs* a, int step, void* stream) {
+  if (a == nullptr || a->P <= 0 || !mlp_shape_supported(a->D0, a->D1, a->D2, a->D3)) return 1;
+  if (a->B <= 0 || a->Bpad < a->B || a->Bpad % 32 != 0 || a->Bpad > MLP_MAX_BPAD) return 1;
+  mlp_launch_train_step(*a, step, (hipStream_t)stream);
+  return hipGetLastError() != hipSuccess;
+}
+
+int mlp_debug_eval_chunk(const MLPArgs* a, int base, void* stream) {
+  if (a == nullptr || a->P <= 0 || !mlp_shape_supported(a->D0, a->D1, a->D2, a->D3)) return 1;
+  mlp_launch_eval_chunk(*a, base, (hipStream_t)stream);
+  return hipGetLastError() != hipSuccess;
+}
+
+}  // extern "C"
