@@ -27,7 +27,8 @@ hipError_t mlp_launch_persistent_epoch(const MLPArgs& a, const MLPPersistBufs& p
 // ---- fp32 variant (mlp_persistent_f32.hip): exact fp32 products, fp32 accumulation and state;
 //      gangs of 16 owners + 8 heads, one launch per group of 8 peers.
 struct MLPPersistF32Bufs {
-  float* h1x;       // [P][Bpad][256]      owner g -> heads: H1 columns 16g..16g+15
+  float* h1x;       // [P][Bpad][256]      owner g -> heads: H1 columns 16g..16g+15; the kernels with the H1 fragment image
+                    // (MYFYP_F32_H1_FRAG) use the same slab as [16 g][Bpad / 16][64 lanes] float4, the heads' MFMA fragments
   float* plx;       // [P][8][Bpad*16][2]  head hd -> heads: partial logits over its H2 slice (sized for (value, tag) pairs)
   float* dh2x;      // [P][2][Bpad][128][2] head hd -> owners: dH2 columns 16hd..16hd+15 (step parity; sized for pairs);
                     // dh2_frag: the first half of each parity slab as [8 hd][Bpad / 16][64 lanes] float4 (see below)

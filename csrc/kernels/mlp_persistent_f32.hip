@@ -30,7 +30,9 @@
 //
 // Per step three hand-offs (persist_common.h): H1 slices owners → heads (16 × 4 KB), partial logits
 // head ↔ head (8 × 4 KB) and dH2 slices heads → owners (8 × 4 KB, double-buffered by step parity
-// because the owners re-read the previous step's tile for their deferred W2-replica update). All
+// because the owners re-read the previous step's tile for their deferred W2-replica update).
+// H1 and dH2 travel as the consumer's MFMA fragments where the kernel is instantiated for it (FRAG,
+// MYFYP_F32_H1_FRAG; pb.dh2_frag, MYFYP_F32_DH2_FRAG) and go from the load straight into registers. All
 // three are flag hand-offs: payload stores, every storing wave drains them, the workgroup meets, one
 // lane stores the flag; the consumer's wave 0 polls the flags, the workgroup meets and reads the
 // payload with L1-bypassing (sc1) loads. A gang found on one XCD at kernel entry
@@ -347,12 +349,15 @@ __device__ __forceinline__ bool gang_commit(const MLPArgs& a, const MLPPersistF3
   return persist::wg_wait(pb.flags, FPP, p, FD, NR, pb.fbase + DONE_MARK, pb.err, sOk);
 }
 
-template <int BP, bool ADAM, bool EXTRA, int KS, bool RH, bool FUSE = false, int K24 = 0>
+template <int BP, bool ADAM, bool EXTRA, int KS, bool RH, bool FUSE = false, int K24 = 0, int FRAG = 0>
 __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, int g, char* smem) {
   // FUSE: the forward of step t + 1 is accumulated inside C2 of step t, K step by K step, by the wave
   // that has just updated that K step's weights and staged its columns of the next batch
   static_assert(!FUSE || (KS == 1 && !RH && !EXTRA), "fused forward: layout 1, K split 1, no extra term");
   static_assert(K24 == 0 || FUSE, "K step 24 in registers: fused forward only");
+  // FRAG: H1 goes to the heads as their MFMA fragments (h1_publish), and dH2 comes as this workgroup's
+  // (pb.dh2_frag is 1 in every launch of these instantiations: mlp_launch_persistent_f32_epoch)
+  static_assert(FRAG == 0 || FUSE, "H1 fragment image: the fused layout-1 K-split-1 kernels only");
   constexpr int MT = BP / 16;
   constexpr int RQ = rq_of(KS);
   constexpr int XPT = BP / 4;  // 16-byte X chunks per lane: 4 K steps x BP rows x 4 chunks / 64 lanes
@@ -491,7 +496,7 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
     // (one step of kb is 4 lanes = 64 bytes on, one batch tile 64 lanes = 1 KB)
     const float* h1p = sH1 + (tp & 1) * BP * 16;
     float av[BP / 4];
-    if (!RH && pb.dh2_frag != 0) {
+    if (FRAG != 0 || (!RH && pb.dh2_frag != 0)) {
       const int ro = 4 * (((wave * MT) * 64 + ((lr & 15) >> 2) * 16 + (lr >> 4)) * 4 + (lr & 3));
 #pragma unroll
       for (int kb = 0; kb < BP / 4; ++kb) av[kb] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rd, ro + 1024 * (kb >> 2) + 64 * (kb & 3), 0, 16));
@@ -580,7 +585,19 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
         // b1 came in through the bias column; KS > 1: a partial sum (relu after the kh-ordered sum)
         const float v = b < rows ? (KS == 1 ? fmaxf(s[i], 0.f) : s[i]) : 0.f;
         sH1c[b * 16 + cc] = v;
-        persist::pub32(pb.plain, h1x_part(pb, p, kh, t, BP) + (unsigned)(b * PD1 + NCG * cg + cc), v);
+        if constexpr (FRAG == 0) persist::pub32(pb.plain, h1x_part(pb, p, kh, t, BP) + (unsigned)(b * PD1 + NCG * cg + cc), v);
+      }
+      if constexpr (FRAG != 0) {
+        // fragment image (MYFYP_F32_H1_FRAG), in the slab the row image has: h1f[g][mt][lane] =
+        // H1[16 mt + c][16 g + 4h .. + 3] (h = lane >> 4, c = lane & 15), the operand of head wave g / 2's
+        // four H2 MFMAs of column group g on batch tile mt, so that a head loads it straight into
+        // registers (one coalesced 1 KB access per wave, group and tile). This wave wrote all 16 rows of
+        // its tile itself: the read-back needs its own LDS stores only, no barrier. One 16-byte store
+        // per lane in front of the flag's drain instead of four 4-byte ones. Rows past the batch are
+        // zero in the image as in the row image.
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        const float4 fr = *reinterpret_cast<const float4*>(sH1c + (16 * mt + cc) * 16 + 4 * hh);
+        persist::pub128(pb.plain, h1x_part(pb, p, 0, t, BP), BP * PD1 * 4, ((cg * MT + mt) * 64 + (tq & 63)) * 16, __builtin_bit_cast(u32x4, fr));
       }
     }
     if (g == 0) P32_STAMP(0, t, 1);
@@ -794,7 +811,7 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
     // this wave's A operands of every batch tile in lane order, so they come straight into registers,
     // one coalesced 1 KB load per tile, with no LDS staging and none of its two barriers. The lane is
     // the step's laundered one (an address hoisted across the step loop would be spilled).
-    const bool frag = !RH && pb.dh2_frag != 0;
+    const bool frag = FRAG != 0 || (!RH && pb.dh2_frag != 0);
     float4 avf[MT];
     if (frag) {
 #pragma unroll
@@ -1125,8 +1142,18 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
 // =============================================================================================
 // head workgroup
 // =============================================================================================
-template <int BP, bool ADAM, bool EXTRA, int KS>
+// FRAG (MYFYP_F32_H1_FRAG; K split 1, no extra term, with the owners' FRAG): the heads' chain without
+// its LDS transposes. H1 arrives as this wave's MFMA fragments (owner32's h1_publish) and goes straight
+// into registers; H2 and dH2 are accumulated TRANSPOSED, by passing the same two registers to
+// v_mfma_f32_16x16x4_f32 in the other order: A is A[lane & 15][k = lane >> 4] and B is
+// B[k = lane >> 4][lane & 15], one float per lane each, so the swap computes the transposed tile from
+// the same k-ordered fmaf chain (fmaf(a, b, c) == fmaf(b, a, c): same bits), and lane (h, c) holds
+// C[row c][column 4h + i] instead of C[row 4h + i][column c]. That is the A operand of the next MFMA
+// (partial logits) and the fragment the owners want (dH2), which the row-major accumulators reached
+// only through an LDS write, a wait (and for H2 a workgroup barrier) and a transposed read.
+template <int BP, bool ADAM, bool EXTRA, int KS, int FRAG = 0>
 __device__ void head32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, int hd, char* smem) {
+  static_assert(FRAG == 0 || (KS == 1 && !EXTRA), "H1 fragment image: K split 1, no extra term");
   constexpr int MT = BP / 16;
   constexpr bool XR = xr_of(KS, false);
   const int tid = threadIdx.x, lane = tid & 63;
@@ -1247,6 +1274,74 @@ __device__ void head32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, int
     constexpr int KSR = XR ? 1 : KS;
     if (!persist::wg_wait(pb.flags, FPP, p, F_H1, XR ? NCG : ng_of(KS), target, pb.err, sOk)) return;
     if (hd == 0) P32_STAMP(1, t, 1);
+    // FRAG, waves < MT: relu(H2 + b2)[16 wave + c][4h .. 4h + 3], kept for the dH2 mask
+    float4 h2v = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (FRAG != 0) {
+      // ---- H1(t) as this wave's fragments (owner32's h1_publish): hf[gg][mt] = H1[16 mt + c][16 g + 4h ..
+      //      + 3], g = 2 wave + gg, straight into the registers the H2 MFMAs take: no staging through
+      //      sH1 and no workgroup barrier behind it (wave w only ever multiplies the columns of owners
+      //      2w and 2w + 1). The lane is the step's laundered one.
+      float4 hf[2][MT];
+      const __amdgpu_buffer_rsrc_t r = rsrc_of(h1x_part(pb, p, 0, t, BP), BP * PD1 * 4);
+#pragma unroll
+      for (int gg = 0; gg < 2; ++gg)
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) hf[gg][mt] = ld_sc1_16(r, (((2 * wave + gg) * MT + mt) * 64 + (tv & 63)) * 16);
+      if (hd == 0) P32_STAMP(1, t, 2);  // (the loads issued, not waited for: their latency is in the next segment)
+      // ---- H2 slice, transposed: acc[mt][i] = Σ over o1 in [32w, 32w + 32) of H1[16 mt + c][o1] ·
+      //      W2[16 hd + 4h + i][o1], the same k order (16 g + 4h + j: j outside, h inside the MFMA)
+      f32x4 acc[MT];
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) acc[mt] = zero4();
+#pragma unroll
+      for (int gg = 0; gg < 2; ++gg) {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+          const float4 av = hf[gg][mt];
+          acc[mt] = mfma_f32(w2[gg][0], av.x, acc[mt]);
+          acc[mt] = mfma_f32(w2[gg][1], av.y, acc[mt]);
+          acc[mt] = mfma_f32(w2[gg][2], av.z, acc[mt]);
+          acc[mt] = mfma_f32(w2[gg][3], av.w, acc[mt]);
+        }
+      }
+      // sRed's previous readers, step t - 1's reducing waves, read it before that step's partial-logit
+      // publish (publish_p's __syncthreads()); this step's wg_wait met the workgroup since.
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) sRed[(wave * MT + mt) * 64 + lane] = acc[mt];
+      lds_barrier();
+      if (tid < MT * 64) {
+        // reducing wave mt = wave: lane (h, c) holds H2[16 mt + c][4h + i] before the bias, which is the A
+        // operand of this wave's partial-logit MFMAs once relu'd: they run from registers. The row-major
+        // accumulators went through sH2 and a workgroup barrier for that (a 16 x 16 transpose). No
+        // barrier here: sH2's other readers are the deferred dW3 (wave 0), behind publish_p's
+        // __syncthreads() below, and its previous ones (step t - 1's dW3) are behind the
+        // __syncthreads() that ended that step; sW3 and sB2 were last written before that barrier too;
+        // sRed is not written again before step t + 1's H2, many barriers on.
+        f32x4 s = sRed[wave * 64 + lane];
+#pragma unroll
+        for (int w = 1; w < 8; ++w) s += sRed[(w * MT + wave) * 64 + lane];
+        const float4 bias = *reinterpret_cast<const float4*>(sB2 + 4 * h);
+        const bool rin = 16 * wave + c < rows;  // the row mask: this lane's row is its c, whatever i
+        h2v = float4{rin ? fmaxf(s[0] + bias.x, 0.f) : 0.f, rin ? fmaxf(s[1] + bias.y, 0.f) : 0.f, rin ? fmaxf(s[2] + bias.z, 0.f) : 0.f,
+                     rin ? fmaxf(s[3] + bias.w, 0.f) : 0.f};
+        *reinterpret_cast<float4*>(sH2 + (16 * wave + c) * LD16 + 4 * h) = h2v;  // for dW3
+        // ---- partial logits of this slice (rows 16w..16w+15; k order o2 = 4h + ks), plx as ever
+        const float4 bv = *reinterpret_cast<const float4*>(sW3 + c * LD16 + 4 * h);
+        f32x4 pl = mfma_f32(h2v.x, bv.x, zero4());
+        pl = mfma_f32(h2v.y, bv.y, pl);
+        pl = mfma_f32(h2v.z, bv.z, pl);
+        pl = mfma_f32(h2v.w, bv.w, pl);
+        persist::pub128(pb.plain, pb.plx + ((int64_t)p * NH + hd) * BP * 16 * 2, BP * 16 * 4, (wave * 64 + lane) * 16, __builtin_bit_cast(u32x4, pl));
+      }
+      // H1 for the deferred dW2, which reads only this wave's own columns 16 g + c of every row: the
+      // wave's own fragments, stored behind its MFMAs and the partial logits' store, off the chain.
+      // Wave-local (sH1's columns of groups 2w and 2w + 1 are written and read by wave w alone, in
+      // program order); the barriers in front of dW2 cover it all the same.
+#pragma unroll
+      for (int gg = 0; gg < 2; ++gg)
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) *reinterpret_cast<float4*>(sH1 + (16 * mt + c) * LDH1 + 16 * (2 * wave + gg) + 4 * h) = hf[gg][mt];
+    } else {
     {
       // every partial's loads issued before any is consumed (one L2 round trip, not KS)
       float4 u[KSR][BP / 8];
@@ -1319,6 +1414,7 @@ __device__ void head32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, int
       // lanes of every head have the same (wave, h, c) and read their rows of the four
       persist::pub128(pb.plain, pb.plx + ((int64_t)p * NH + hd) * BP * 16 * 2, BP * 16 * 4, (wave * 64 + lane) * 16, __builtin_bit_cast(u32x4, pl));
     }
+    }  // FRAG == 0 (kept at its indentation)
     if (hd == 0) P32_STAMP(1, t, 3);
     persist::publish_p(pb.flags, FPP, p, F_PL + hd, target, pb.plain);
     if (!persist::wg_wait(pb.flags, FPP, p, F_PL, NH, target, pb.err, sOk)) return;
@@ -1374,7 +1470,21 @@ __device__ void head32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, int
     if (sOk[1] == 0) return;  // (never taken: see sOk[1] above)
     if (hd == 0) P32_STAMP(1, t, 6);
     // ---- dH2 slice = dlogits · W3[:, slice] ⊙ [H2 > 0]  (K = classes, natural order)
-    if (wave < MT) {
+    if (FRAG != 0 && wave < MT) {
+      // transposed (operands swapped, the same k order over the classes): acc[i] = dH2[16 wave + c][16 hd
+      // + 4h + i] before the mask, which is the owners' fragment itself (the image below, always the
+      // fragment one here): masked with this lane's own H2 values, published with one 16-byte store, and
+      // stored for dW2 and db2 in front of publish_p's barrier. sDH2's previous readers (step t - 1's
+      // dW2 and db2) are behind the __syncthreads() that ended that step.
+      f32x4 acc = zero4();
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) acc = mfma_f32(sW3[(4 * ks + h) * LD16 + c], sDlog[(16 * wave + c) * LD16 + 4 * ks + h], acc);
+      const float4 fr = {h2v.x > 0.f ? acc[0] : 0.f, h2v.y > 0.f ? acc[1] : 0.f, h2v.z > 0.f ? acc[2] : 0.f, h2v.w > 0.f ? acc[3] : 0.f};
+      persist::pub128(pb.plain_x, pb.dh2x + ((int64_t)p * 2 + (t & 1)) * BP * PD2 * 2, BP * PD2 * 4, ((hd * MT + wave) * 64 + (tv & 63)) * 16,
+                      __builtin_bit_cast(u32x4, fr));
+      *reinterpret_cast<float4*>(sDH2 + (16 * wave + c) * LD16 + 4 * h) = fr;
+    }
+    if (FRAG == 0 && wave < MT) {
       f32x4 acc = zero4();
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) acc = mfma_f32(sDlog[(16 * wave + c) * LD16 + 4 * ks + h], sW3[(4 * ks + h) * LD16 + c], acc);
@@ -1481,11 +1591,26 @@ __device__ void head32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, int
     a.m[idx] = sB3[16 + k];
     if (ADAM) a.v[idx] = sB3[32 + k];
   }
-  if (hd == 0 && wave < MT * (4 / SMR)) {
+  if (hd == 0) {
+    // the softmax waves' sums, added in wave order by one thread: one float atomicAdd per wave landed in
+    // arrival order, and the epoch's loss sum differed in its last bits from run to run and between two
+    // builds that compute the same values (sRed is free: the step loop's last barrier and the commit's
+    // are behind every read of it)
+    float* sSum = reinterpret_cast<float*>(sRed);
     const float l = wave_sum(loss_acc), cr = wave_sum(correct_acc);
     if (lane == 0) {
-      atomicAdd(&a.loss_acc[p], l);
-      atomicAdd(&a.correct_acc[p], (int)(cr + 0.5f));
+      sSum[2 * wave] = l;
+      sSum[2 * wave + 1] = cr;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      float ls = 0.f, cs = 0.f;
+      for (int w = 0; w < MT * (4 / SMR); ++w) {
+        ls += sSum[2 * w];
+        cs += sSum[2 * w + 1];
+      }
+      atomicAdd(&a.loss_acc[p], ls);
+      atomicAdd(&a.correct_acc[p], (int)(cs + 0.5f));
     }
   }
 }
@@ -1849,7 +1974,7 @@ __device__ void headr32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
 // flags offset by RETRY_BASE (the aborted attempt's flag values are all smaller), and on success
 // sets err[p] = 2 ("recovered"). Gangs are independent: one peer's give-up never aborts another.
 
-template <int BP, bool ADAM, bool EXTRA, int KS, bool RH = false, bool FUSE = false, int K24 = 0>
+template <int BP, bool ADAM, bool EXTRA, int KS, bool RH = false, bool FUSE = false, int K24 = 0, int FRAG = 0>
 __global__ __launch_bounds__(NT) void mlp_persistent_f32_epoch(MLPArgs a, MLPPersistF32Bufs pb, int p_base, int attempt) {
   extern __shared__ __attribute__((aligned(16))) char smem_p32[];
   constexpr int PPL = ppl_of(KS, RH);
@@ -1917,11 +2042,11 @@ __global__ __launch_bounds__(NT) void mlp_persistent_f32_epoch(MLPArgs a, MLPPer
     if (role == 0 && threadIdx.x == 0 && p < 64) g_plain_seen[p] = pb.plain;
   }
   if (role < ng_of(KS))
-    owner32<BP, ADAM, EXTRA, KS, RH, FUSE, K24>(a, pb, p, role, smem_p32);
+    owner32<BP, ADAM, EXTRA, KS, RH, FUSE, K24, FRAG>(a, pb, p, role, smem_p32);
   else if (RH)
     headr32<BP, ADAM, EXTRA, KS>(a, pb, p, role - ng_of(KS), smem_p32);
   else
-    head32<BP, ADAM, EXTRA, KS>(a, pb, p, role - ng_of(KS), smem_p32);
+    head32<BP, ADAM, EXTRA, KS, FRAG>(a, pb, p, role - ng_of(KS), smem_p32);
   if (role == 0) {
     __syncthreads();
     if (!attempt) P32_ESTAMP(3);
@@ -2140,9 +2265,9 @@ bool v3_supported(const MLPArgs& a) {
   return persistent_f32_lds_ks(a, 1, true) <= 160 * 1024;
 }
 
-template <int BP, bool ADAM, bool EXTRA, int KS, bool RH = false, bool FUSE = false, int K24 = 0>
+template <int BP, bool ADAM, bool EXTRA, int KS, bool RH = false, bool FUSE = false, int K24 = 0, int FRAG = 0>
 const void* f32_fn() {
-  return (const void*)mlp_persistent_f32_epoch<BP, ADAM, EXTRA, KS, RH, FUSE, K24>;
+  return (const void*)mlp_persistent_f32_epoch<BP, ADAM, EXTRA, KS, RH, FUSE, K24, FRAG>;
 }
 // the fused forward (owner32's FUSE) is instantiated for layout 1 at K split 1 without an extra term
 __host__ __device__ constexpr bool fuse_inst(int KS, bool RH) { return KS == 1 && !RH; }
@@ -2155,8 +2280,11 @@ hipError_t prepare_f32_bp(int lds) {
     if (e != hipSuccess) return e;
   }
   if constexpr (fuse_inst(KS, RH)) {
+    // (the last argument: the H1 fragment image, launch_f32_bp)
     for (const void* fn : {f32_fn<BP, true, false, KS, RH, true>(), f32_fn<BP, false, false, KS, RH, true>(),
-                           f32_fn<BP, true, false, KS, RH, true, 1>(), f32_fn<BP, false, false, KS, RH, true, 1>()}) {
+                           f32_fn<BP, true, false, KS, RH, true, 1>(), f32_fn<BP, false, false, KS, RH, true, 1>(),
+                           f32_fn<BP, true, false, KS, RH, true, 0, 1>(), f32_fn<BP, false, false, KS, RH, true, 0, 1>(),
+                           f32_fn<BP, true, false, KS, RH, true, 1, 1>(), f32_fn<BP, false, false, KS, RH, true, 1, 1>()}) {
       const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
       if (e != hipSuccess) return e;
     }
@@ -2164,11 +2292,21 @@ hipError_t prepare_f32_bp(int lds) {
   return hipSuccess;
 }
 template <int BP, int KS, bool RH = false>
-void launch_f32_bp(const MLPArgs& a, const MLPPersistF32Bufs& pb, hipStream_t s, int p_base, size_t lds, int attempt, bool fuse) {
+void launch_f32_bp(const MLPArgs& a, const MLPPersistF32Bufs& pb, hipStream_t s, int p_base, size_t lds, int attempt, bool fuse, bool h1_frag) {
   const dim3 grid(grid_of(KS, RH, RH ? roles3_of(KS, BP) : roles_of(KS))), block(NT);
   const bool adam = a.opt.kind == 0;
   const bool extra = a.anchor != nullptr || a.cg != nullptr;
   if constexpr (fuse_inst(KS, RH)) {
+    if (fuse && !extra && h1_frag) {  // H1 and dH2 as fragment images (set by the launch where it applies)
+      if (pb.k24 == 1) {
+        if (adam) hipLaunchKernelGGL((mlp_persistent_f32_epoch<BP, true, false, KS, RH, true, 1, 1>), grid, block, lds, s, a, pb, p_base, attempt);
+        else hipLaunchKernelGGL((mlp_persistent_f32_epoch<BP, false, false, KS, RH, true, 1, 1>), grid, block, lds, s, a, pb, p_base, attempt);
+      } else {
+        if (adam) hipLaunchKernelGGL((mlp_persistent_f32_epoch<BP, true, false, KS, RH, true, 0, 1>), grid, block, lds, s, a, pb, p_base, attempt);
+        else hipLaunchKernelGGL((mlp_persistent_f32_epoch<BP, false, false, KS, RH, true, 0, 1>), grid, block, lds, s, a, pb, p_base, attempt);
+      }
+      return;
+    }
     if (fuse && !extra && pb.k24 == 1) {  // K step 24 register-resident (set by the launch where it applies)
       if (adam) hipLaunchKernelGGL((mlp_persistent_f32_epoch<BP, true, false, KS, RH, true, 1>), grid, block, lds, s, a, pb, p_base, attempt);
       else hipLaunchKernelGGL((mlp_persistent_f32_epoch<BP, false, false, KS, RH, true, 1>), grid, block, lds, s, a, pb, p_base, attempt);
@@ -2401,6 +2539,29 @@ static int f32_dh2_frag_mode() {
 extern "C" int mlp_set_f32_dh2_frag(int mode) { return g_dh2_frag_override.exchange(mode < 0 ? -1 : mode); }
 extern "C" int mlp_f32_dh2_frag_last() { return g_dh2_frag_last.load(std::memory_order_relaxed); }
 
+// MYFYP_F32_H1_FRAG: 1 (default) the owners of layout 1 publish H1 as the heads' MFMA fragments
+// (h1f[parity][g][mt][lane], one 16-byte store per lane), the heads load them straight into registers
+// and accumulate H2 and dH2 transposed, 0 the [b][256] image staged through LDS and the row-major
+// accumulators (A/B; same bits either way); mlp_set_f32_h1_frag overrides it (tests; -1: back to the
+// environment). Values above 1 are taken as 1. A template argument of the kernel, not a launch
+// argument (head32's FRAG): it is taken only where the fused layout-1 K-split-1 kernels are launched
+// and dH2 goes as fragments too (MYFYP_F32_DH2_FRAG). mlp_f32_h1_frag_last: what the last epoch launch
+// took: 0 for layouts 2 and 3, K splits > 1, extra-term epochs, the separate forward and with either
+// switch off (-1: none yet).
+static std::atomic<int> g_h1_frag_override{-1};
+static std::atomic<int> g_h1_frag_last{-1};
+static int f32_h1_frag_mode() {
+  const int o = g_h1_frag_override.load(std::memory_order_relaxed);
+  if (o >= 0) return o;
+  static const int v = [] {
+    const char* e = getenv("MYFYP_F32_H1_FRAG");
+    return e != nullptr ? atoi(e) : 1;
+  }();
+  return v;
+}
+extern "C" int mlp_set_f32_h1_frag(int mode) { return g_h1_frag_override.exchange(mode < 0 ? -1 : mode); }
+extern "C" int mlp_f32_h1_frag_last() { return g_h1_frag_last.load(std::memory_order_relaxed); }
+
 hipError_t mlp_launch_persistent_f32_epoch(const MLPArgs& a, const MLPPersistF32Bufs& pb_in, hipStream_t s, bool zero_flags, const int* active) {
   MLPPersistF32Bufs pb = pb_in;
   pb.plain_ok = mlp_plain_pub_mode();
@@ -2412,6 +2573,7 @@ hipError_t mlp_launch_persistent_f32_epoch(const MLPArgs& a, const MLPPersistF32
     if (e != hipSuccess) return e;
   }
   if (f32_variant(a) == 2) {
+    g_h1_frag_last.store(0, std::memory_order_relaxed);
     mlp_f32v2_launch(a, pb, s);
     return hipGetLastError();
   }
@@ -2426,6 +2588,8 @@ hipError_t mlp_launch_persistent_f32_epoch(const MLPArgs& a, const MLPPersistF32
   g_straight_last.store(straight_all ? 1 : 0, std::memory_order_relaxed);
   pb.k24 = f32_k24_mode() > 0 && fuse && straight_all && 8 * rq_of(1) < ks1_of(a.D0) ? 1 : 0;
   g_k24_last.store(pb.k24, std::memory_order_relaxed);
+  const bool h1_frag = f32_h1_frag_mode() > 0 && fuse && pb.dh2_frag == 1;
+  g_h1_frag_last.store(h1_frag ? 1 : 0, std::memory_order_relaxed);
   // groups of ppl peers: one launch each (a launch's gangs must all be co-resident), then the
   // recovery launches (attempt 1): a no-op exit for every gang that did not give up
   // (a group with no active peer is not launched: at one peer per device and K split 8 the other
@@ -2442,22 +2606,22 @@ hipError_t mlp_launch_persistent_f32_epoch(const MLPArgs& a, const MLPPersistF32
       if (!group_live(p0)) continue;
       if (rh) {
         if (KS == 2) {
-          if (a.Bpad == 64) launch_f32_bp<64, 2, true>(a, pb, s, p0, lds, attempt, fuse);
-          else launch_f32_bp<32, 2, true>(a, pb, s, p0, lds, attempt, fuse);
+          if (a.Bpad == 64) launch_f32_bp<64, 2, true>(a, pb, s, p0, lds, attempt, fuse, h1_frag);
+          else launch_f32_bp<32, 2, true>(a, pb, s, p0, lds, attempt, fuse, h1_frag);
         } else {
-          if (a.Bpad == 64) launch_f32_bp<64, 1, true>(a, pb, s, p0, lds, attempt, fuse);
-          else launch_f32_bp<32, 1, true>(a, pb, s, p0, lds, attempt, fuse);
+          if (a.Bpad == 64) launch_f32_bp<64, 1, true>(a, pb, s, p0, lds, attempt, fuse, h1_frag);
+          else launch_f32_bp<32, 1, true>(a, pb, s, p0, lds, attempt, fuse, h1_frag);
         }
       } else if (KS == 8) {
-        launch_f32_bp<64, 8>(a, pb, s, p0, lds, attempt, fuse);  // (f32_ks_wanted: Bpad 64 only)
+        launch_f32_bp<64, 8>(a, pb, s, p0, lds, attempt, fuse, h1_frag);  // (f32_ks_wanted: Bpad 64 only)
       } else if (KS == 4) {
-        launch_f32_bp<64, 4>(a, pb, s, p0, lds, attempt, fuse);
+        launch_f32_bp<64, 4>(a, pb, s, p0, lds, attempt, fuse, h1_frag);
       } else if (KS == 2) {
-        if (a.Bpad == 64) launch_f32_bp<64, 2>(a, pb, s, p0, lds, attempt, fuse);
-        else launch_f32_bp<32, 2>(a, pb, s, p0, lds, attempt, fuse);
+        if (a.Bpad == 64) launch_f32_bp<64, 2>(a, pb, s, p0, lds, attempt, fuse, h1_frag);
+        else launch_f32_bp<32, 2>(a, pb, s, p0, lds, attempt, fuse, h1_frag);
       } else {
-        if (a.Bpad == 64) launch_f32_bp<64, 1>(a, pb, s, p0, lds, attempt, fuse);
-        else launch_f32_bp<32, 1>(a, pb, s, p0, lds, attempt, fuse);
+        if (a.Bpad == 64) launch_f32_bp<64, 1>(a, pb, s, p0, lds, attempt, fuse, h1_frag);
+        else launch_f32_bp<32, 1>(a, pb, s, p0, lds, attempt, fuse, h1_frag);
       }
     }
   return hipGetLastError();

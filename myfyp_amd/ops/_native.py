@@ -120,6 +120,8 @@ _SIGNATURES = {
     "mlp_f32_k24_last": (c_int, []),  # 1: the last fp32 layout-1 epoch launch ran K step 24 from registers
     "mlp_set_f32_dh2_frag": (c_int, [c_int]),  # dH2 handed over in MFMA fragment order: 1 / 0 (-1: MYFYP_F32_DH2_FRAG)
     "mlp_f32_dh2_frag_last": (c_int, []),  # 1: the last fp32 epoch launch took it (0: layouts 2 / 3 or switched off)
+    "mlp_set_f32_h1_frag": (c_int, [c_int]),  # H1 handed over in MFMA fragment order, H2 / dH2 transposed: 1 / 0 (-1: MYFYP_F32_H1_FRAG)
+    "mlp_f32_h1_frag_last": (c_int, []),  # 1: the last fp32 epoch launch took it (fused layout-1 K-split-1 kernels, dH2 fragments on)
     # direct drive of the step-path kernels on a caller-built MLPArgs (tests/test_mlp_fused_gpu.py)
     "mlp_debug_args_size": (c_int, []),
     "mlp_debug_args_abi": (c_int, [c_void_p]),
