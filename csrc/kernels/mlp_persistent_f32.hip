@@ -4,15 +4,22 @@
 // lightning_learner.py:82-89, lightning_model.py:181-183), uint8 pixels cast to float
 // (lightning_model.py:187).
 //
-// Arithmetic. Every product is an exact fp32 product and every sum an fp32 sum:
+// Arithmetic. Layouts 1 and 2: every product is an exact fp32 product and every sum an fp32 sum
+// (layout 3's H2 is the one exception, below):
 //   * X·W1ᵀ (forward) and dH1ᵀ·X (dW1): X is uint8, so exact in bf16. The fp32 operand is split
 //     EXACTLY into three bf16 terms (hi + mid + lo carry its 24 significand bits, split3 below),
 //     so three v_mfma_f32_16x16x32_bf16 against the exact-bf16 X give exact products accumulated
 //     in fp32 — at 3/16 of the cost of the f32-input MFMA for the two 12.5k-element GEMMs that
-//     dominate the step.
+//     dominate the step. The bf16 MFMA's fp32 accumulation rounds FAITHFULLY, not to nearest:
+//     with one batch row dW1 = lo·x + mid·x (exact) + hi·x is the correctly rounded dH1·x in
+//     99.7 % of the elements and its other fp32 neighbour in the rest (MI355X,
+//     tests/test_mlp_f32_oracle_gpu.py); a sum the fp32 format holds exactly comes out exact.
 //   * every other GEMM (H2, logits, dH2, dH1, dW2, dW3, bias column sums) runs on
 //     v_mfma_f32_16x16x4_f32: f32 in, f32 accumulate, bit-for-bit a k-ordered fmaf chain
 //     (cdna_hip_programming.md §3 'FP32-input MFMA').
+//   * layout 3 (row heads) computes H2 on the bf16 MFMA with BOTH operands split and keeps six of the
+//     nine cross terms: the dropped mid·lo + lo·mid + lo·lo are at most (2^-23 + 2^-32)·|a·b| per
+//     product (headr32), about one fp32 ulp of it.
 //   * fp32 master weights and Adam moments live in registers for the whole epoch, hand-offs are
 //     fp32.
 //
@@ -1642,7 +1649,10 @@ __host__ __device__ inline HeadRLds32 headr_lds32() {
 //   H2 rows   = relu(H1 rows · W2ᵀ + b2): wave w computes the 16 columns 16w..16w+15 against W2 rows
 //               it loads itself (the owners' published columns, or the epoch's initial W2); both
 //               fp32 operands split exactly into bf16 hi / mid / lo, six bf16 MFMA terms per 32-wide
-//               K step (the three dropped cross terms are below 2^-32 of the product);
+//               K step. The three dropped cross terms mid·lo + lo·mid + lo·lo: bf16 has 8 significant
+//               bits, so |mid| <= 2^-8 |x| and |lo| <= 2^-16 |x|, and they sum to at most
+//               (2^-23 + 2^-32) |a·b| per product — up to one fp32 ulp of it (2^-24.6 seen on random
+//               operands), not 2^-32; zero where both operands have at most 16 significant bits;
 //   logits    = per-wave partials over its 16 H2 columns (f32 MFMA), summed over the waves in order;
 //   softmax / NLL / dlogits of the 16 rows (one wave, DPP row reductions, as layout 1);
 //   dH2 rows  = dlogits · W3 ⊙ [H2 > 0] -> the owners (the step's only head -> owner hand-off);

@@ -498,19 +498,46 @@ def mm32_permuted(g):
     return mm
 
 
-def sgd_epoch(W, x, y, perm, B, lr, rnd=bf16, mm=mm64, f32=False):
+def _opt_f32(hp, w, g, m, v, k):
+    """One ``torch.optim`` step of one tensor with every operation in fp32 (the twin's optimizer). ``k``: the step count
+    from 1. Returns ``(w', m', v')`` as float64 values of fp32 numbers."""
+    t = lambda a: torch.tensor(R.f32(a), dtype=F32)
+    w, g = w.float(), g.float()
+    wd = hp.get("wd", 0.0)
+    if wd != 0.0:
+        g = g + t(wd) * w
+    if hp["kind"] == 0:
+        b1, b2 = R.f32(BETA1), R.f32(BETA2)
+        m = t(b1) * m.float() + t(1.0 - b1) * g
+        v = t(b2) * v.float() + t(1.0 - b2) * g * g
+        w = w - t(R.f32(hp["lr"]) / (1.0 - b1 ** k)) * (m / (v.sqrt() * t(1.0 / math.sqrt(1.0 - b2 ** k)) + t(EPS)))
+        return w.double(), m.double(), v.double()
+    mom = hp.get("momentum", 0.0)
+    if mom != 0.0:
+        m = t(mom) * m.float() + g
+        g = g + t(mom) * m if hp.get("nesterov", False) else m
+        m = m.double()
+    return (w - t(hp["lr"]) * g).double(), m, v
+
+
+def epoch(W, x, y, perm, B, hp, rnd=bf16, mm=mm64, f32=False, state=None):
     """``W``: one peer's ``{name: float64}`` master values, ``x`` ``[n, D0]``, ``y`` ``[n]``, ``perm`` the epoch order. One pass in
-    batches of ``B`` (the last one partial), ``w -= fp32(lr) * g`` after each; the bf16 roundings of :func:`step` and no
-    other. Returns the new master values.
+    batches of ``B`` (the last one partial), one step of the optimizer ``hp`` (an ``OPT_VARIANTS`` entry without extras,
+    through :func:`opt_step`) after each; the bf16 roundings of :func:`step` and no other (``rnd = ident``: none at all).
+    ``state``: ``(m, v, steps done)`` of an earlier epoch of the same fit (default: zero moments, no step done).
+    Returns ``(W', (m', v', steps done))``.
 
     ``f32`` (with ``mm = mm32_permuted(g)``): everything the kernels hold in fp32 is fp32 here too: every sum (the
-    products, the bias gradients, the softmax) accumulated in fp32, in another order where ``mm`` does it, and the
-    master row rounded to fp32 after each update. Against the float64 run this measures the oracle's own
-    sensitivity: the floor below which two correct fp32 implementations of the epoch cannot be told apart."""
+    products, the bias gradients, the softmax) accumulated in fp32, in another order where ``mm`` does it, the
+    optimizer in fp32 arithmetic and the master row and the moments rounded to fp32 after each update. Against the
+    float64 run this measures the oracle's own sensitivity: the floor below which two correct fp32 implementations
+    of the epoch cannot be told apart."""
     W = {k: v.clone() for k, v in W.items()}
     D3 = W["b3"].shape[0]
-    lr = R.f32(lr)
     zero = torch.zeros((), dtype=F64)
+    if state is None:
+        state = ({k: torch.zeros_like(v) for k, v in W.items()}, {k: torch.zeros_like(v) for k, v in W.items()}, 0)
+    m, v, done = dict(state[0]), dict(state[1]), state[2]
     for s in range(0, len(perm), B):
         idx = torch.as_tensor(perm[s: s + B], dtype=torch.int64)
         X, yy = x[idx].double(), y[idx].long()
@@ -531,10 +558,360 @@ def sgd_epoch(W, x, y, perm, B, lr, rnd=bf16, mm=mm64, f32=False):
         bsum = (lambda t: mm(t.t(), one)[:, 0]) if f32 else (lambda t: t.sum(0))
         g = {"W1": mm(dH1.t(), X), "b1": bsum(dH1), "W2": mm(dH2.t(), H1), "b2": bsum(dH2), "W3": mm(dl.t(), H2), "b3": bsum(dl)}
         for k in W:
-            W[k] = (W[k].float() - torch.tensor(lr, dtype=F32) * g[k].float()).double() if f32 else W[k] - lr * g[k]
-    return W
+            if f32:
+                W[k], m[k], v[k] = _opt_f32(hp, W[k], g[k], m[k], v[k], done + 1)
+            else:
+                o = opt_step(dict(hp, t0=0), W[k].numpy(), g[k].numpy(), m[k].numpy(), v[k].numpy(), done)
+                W[k] = torch.from_numpy(np.asarray(o[0], dtype=np.float64))
+                m[k] = m[k] if o[1] is None else torch.from_numpy(np.asarray(o[1], dtype=np.float64))
+                v[k] = v[k] if o[2] is None else torch.from_numpy(np.asarray(o[2], dtype=np.float64))
+        done += 1
+    return W, (m, v, done)
+
+
+def sgd_epoch(W, x, y, perm, B, lr, rnd=bf16, mm=mm64, f32=False):
+    """One epoch of plain SGD, ``w -= fp32(lr) * g`` after each batch: :func:`epoch` with that optimizer. Returns the
+    new master values."""
+    return epoch(W, x, y, perm, B, dict(kind=1, lr=lr, momentum=0.0, wd=0.0, nesterov=False), rnd, mm, f32)[0]
 
 
 def rel_update(got, ref, start):
     """``|(got - start) - (ref - start)| / |ref - start|`` in the 2-norm: the relative update error of one tensor."""
     return float(((got - start) - (ref - start)).norm() / ((ref - start).norm() + 1e-300))
+
+
+# ---------------------------------------------------------------------------------------------
+# the fp32 epoch kernels (mlp_persistent_f32.hip, mlp_persistent_f32v2.hip) and mlp_eval_f32
+# ---------------------------------------------------------------------------------------------
+# D1 = 256 and D2 = 128 are fixed there. What follows is the float64 model (``rnd = ident``) with the per-element
+# bounds of those kernels' fp32 arithmetic, u = 2^-24, gamma(k) = k u / (1 - k u).
+#
+# Forward. On the ``exact`` / ``exact_tie`` weight family with the pixel family above every term of H1, H2 and the
+# logits is an integer multiple of ``units(D)``'s grid and ``sum |term| / unit < 2^24`` (:func:`grid_ratios`), so
+# every fp32 partial sum is exact in ANY order, whichever way the K steps, the K parts, the waves and the heads
+# split it: the kernel's H1, H2 and logits ARE the float64 ones, and with them the relu masks, the first maximum
+# and the ties. W1 / b1 reach the bf16 MFMA as ``split3``'s hi + mid + lo (exact), X as bf16 (exact).
+#
+# Layout 3's H2 (``headr32``) splits BOTH operands and keeps six of the nine cross terms. bf16 has 8 significant
+# bits, so RNE leaves ``|mid| <= 2^-8 |x|`` and ``|lo| <= 2^-16 |x|``; the dropped ``mid lo + lo mid + lo lo`` are at most
+# ``(2^-23 + 2^-32) |a b|`` per product (:data:`L3_DROP`; the worst case, reached when both remainders sit at half
+# an ulp: about one fp32 ulp of the product, not 2^-32 of it). On the grid H1 has at most 16 significant bits
+# and W2 at most 3: ``lo(H1) = mid(W2) = lo(W2) = 0``, the dropped terms vanish and H2 is exact there too.
+# :func:`h2_l3` emulates the six terms; :func:`h2_l3_bound` is the bound for arbitrary fp32 operands.
+#
+# Softmax / dlogits. Layout 1's heads: ``e = __expf(z - mx)`` (``v_exp_f32``), ``se`` by a 4-level butterfly,
+# ``p = e * v_rcp_f32(se)``, ``d = p / rows`` and for the true class ``-(sum_{c != y} p_c) / rows`` (a second butterfly);
+# ``logp = z - (mx + __logf(se))`` for the loss, as ``mlp_head``: ``eps_lp`` of the module docstring holds unchanged.
+# With R the row's logit range: ``z - mx`` rounds once (u R on the exponent), ``__expf`` is ``e_exp = 2 u (1 + R)``:
+# ``a = e_exp + u R`` relative on e; se adds 4 u; ``v_rcp_f32`` 1 ulp = 2 u (the CDNA ISA reference's figure, the source
+# the module docstring cites for ``v_exp`` / ``v_log``); the product u: p is off by ``2 a + 7 u`` (relative, p <= 1);
+# the true class's butterfly 4 u more on a sum <= 1; the IEEE division by rows u:
+# ``eps_A = 2 a + 12 u``. Layouts 2 and 3 (and no other instruction sequence exists) use the library ``expf`` / ``logf``
+# (1 ulp each, within what ``eps_lp`` allows the fast pair) and ``p = expf(logp)``: ``eps_lp`` on the argument acts on
+# p <= 1, ``expf`` 2 u, the butterfly 4 u, the division u: ``eps_B = eps_lp + 7 u``. :func:`eps_softmax32` returns
+# ``eps_dl = max(eps_A, eps_B)``: ``|rows * dlogits - (softmax - onehot)| <= eps_dl`` for every layout.
+#
+# Backward. A sum of K products in ANY order (any split into partial sums; additions of exact zeros are exact) is
+# off by at most ``gamma(K) sum |term|``: each term passes one product rounding at most (none in an fma chain) and at
+# most K - 1 additions. With exact masks, recursively (:func:`bounds32`):
+#   ``e_dl = eps_dl / rows``
+#   ``e_dH2 = [H2 > 0] (gamma(16) |dl| |W3| + e_dl colsum |W3|)``         (f32 MFMA over the 16 class slots)
+#   ``e_dH1 = [H1 > 0] (gamma(128) |dH2| |W2| + e_dH2 |W2|)``
+#   ``dW3, db3, dW2, db2``: ``gamma(rows) sum |term| + sum_r e(upstream)[r] |other operand[r]|``   (f32 MFMA over the batch)
+#   ``dW1, db1``: dH1 enters as hi + mid + lo against the exact X (column D0 = 1 carries db1): ``3 rows`` exact products,
+#   ``sum |term| <= (1 + 2^-7) |dH1| X``: ``(gamma(3 rows) + 12 u) (1 + 2^-7) sum |term| + sum_r e_dH1[r] X[r]``. The 12 u: neither
+#   guide nor the ISA reference says how ``v_mfma_f32_16x16x32_bf16`` rounds when it adds its 32 products to C, and the
+#   one-row check below finds it one ulp off the correctly rounded sum in 0.3 % of the elements; so each of the
+#   at most 6 such instructions an element passes (3 terms x 2 batch tiles of 32 rows) is taken as faithful only:
+#   2 u of the sum of the sizes of everything added so far.
+# Everything is evaluated on the oracle's own values; the kernel's differ from them by the bounds themselves, a
+# second-order term below 2^-10 of each bound: the factor :data:`SECOND`.
+#
+# One valid row. The other rows of dlogits, dH2 and dH1 are exact zeros, so db3, db2 and db1 ARE the kernel's
+# dlogits, dH2 and dH1 of that row (db1: ``lo + mid + hi`` against the bias input 1 reassembles dH1 exactly), and dW3 and
+# dW2 are their products with the exact H2 and H1 rounded ONCE, bit for bit: the f32 MFMA's fma onto 0
+# (:func:`outer32`). For dW1 ``lo x`` is exact (16 bits), ``+ mid x`` is exact (``(mid + lo) x`` has at most 16 + 8 bits) and
+# ``+ hi x`` is the one inexact addition, of the exact ``dH1 x``. If the bf16 MFMA rounded that sum to nearest, dW1 would
+# be ``outer32`` too. MI355X: it is in 99.7 % of the elements and the OTHER fp32 neighbour of the exact product in
+# the rest (658 of 200 704 at D0 = 784 in layout 1 at every K split, 846 in layouts 2 and 3), so the instruction
+# rounds faithfully, not to nearest, and the check is the faithful one: ``|dW1 - dH1 x| <= 2^-23 |dH1 x|``, one ulp at
+# most (:data:`FAITHFUL`). db1 passes the same split, so a term missing from the split is missing from both and
+# cannot show in that comparison: the GPU test looks at db1's low significand byte for it. The K splits divide X's
+# columns, never the batch: the same holds in every layout. fp32 denormals are left out of the bit comparison:
+# below 2^-100 the check is an absolute 2^-100.
+#
+# ``upd32`` (mlp_f32_common.h), one element, every operation an fma or a single rounded product (:func:`upd32`):
+#   ``g1 = fma(wdmu, w, g)``: u |g1| (exact when wdmu = 0); FedProx ``e = fl(-mu anchor)``: u |e|, ``g2 = g1 + e``: u |g2|;
+#   SGD: ``m' = fma(mom, m, g)``: u |m'| + dg; Nesterov ``g' = fma(mom, m', g)``: u |g'| + mom bm + dg; ``w' = fma(-lr, g', w)``:
+#   u |w'| + lr dg'; SCAFFOLD ``e = fl(cg - cl)``, ``w'' = fma(-lr, e, w')``: u |w''| + lr u |e| more.
+#   Adam: ``1 - beta`` is exact in fp32 (Sterbenz); ``m' = fma(b1, m, fl(c1 g))``: u |m'| + u c1 |g| + c1 dg;
+#   ``v' = fma(b2, v, fl(c2 fl(g g)))``: u v' + c2 (2 u g^2 + 2 |g| dg);
+#   ``den = fma(v_sqrt_f32(v'), inv, eps)``: ``v_sqrt_f32`` 1 ulp = 2 u (same source), ``inv = fp32(1 / sqrt(1 - b2^k))`` formed
+#   in double and trusted to 1 ulp (2 u): d_den = inv d_sq + 2 u sq inv + u den with
+#   d_sq = 2 u sq + min(sqrt(bv), bv / sq) (+ 2^-60: a denormal v' may be flushed, sqrt <= 2^-63);
+#   ``q = fl(m' v_rcp_f32(den))``: dq = bm / den + |q| (d_den / den + 2 u + u); ``w' = fma(-lr_t, q, w)`` with ``lr_t =
+#   fp32(lr / (1 - b1^k))`` to 1 ulp: bw = u |w'| + lr_t dq + 2 u lr_t |q|.
+# These are NOT ``opt_update``'s unit counts (``_fl_ops_ref``): that code divides and calls ``sqrtf``.
+#
+# Loss sum. Each valid row adds ``-logp``, off by ``eps_lp``; the lanes, waves and epochs add the n terms in fp32 in
+# some tree: ``n eps_lp + gamma(n) sum loss`` (:func:`loss_bound`). The same for ``mlp_eval_f32`` (library ``expf`` / ``logf``).
+SECOND = 1.0 + 2.0 ** -10
+L3_DROP = 2.0 ** -23 + 2.0 ** -32
+PD1, PD2 = 256, 128
+TINY32 = 2.0 ** -100
+FAITHFUL = 2.0 ** -23  # one fp32 ulp, relative: the bf16 MFMA's accumulation (section comment)
+
+
+# ``randn32``: the ``randn`` family with each tensor scaled by a power of two (the product of the three matrices' factors is
+# 1: the logits keep their size). At lr 1e-4 the unscaled family's updates of the biases, of W2 and of W3 over 3
+# steps are of the order of the fp32 rounding of the master row itself (the twin's floor was 1e-3 for b1 and
+# 5e-4 for W2 at D0 = 40); with these factors every tensor's floor is below 1e-4 (asserted by
+# ``test_mlp_ref_cpu.py`` for every case of part (d)).
+RANDN32_SCALE = {"W1": 16.0, "W2": 0.125, "W3": 0.5, "b1": 2.0 ** -10, "b2": 2.0 ** -10, "b3": 2.0 ** -10}
+
+# The cases of tests/test_mlp_f32_oracle_gpu.py: shapes (D0, D3, B), layouts (gang layout, owner K split, the H1 / dH2
+# fragment switches), and the training rows of the two peers.
+F32_MAIN, F32_RAGGED = (784, 10, 64), (40, 16, 24)
+F32_SHAPES = [F32_MAIN, F32_RAGGED, (8, 1, 32), (32, 10, 24), (792, 16, 32), (784, 1, 24)]  # every D0, D3 and B on the shipping layout
+F32_LAYOUTS = {"v1ks1": (1, 1, -1), "v1ks1_rows": (1, 1, 0), "v1ks2": (1, 2, -1), "v1ks4": (1, 4, -1), "v1ks8": (1, 8, -1), "v2": (2, 1, -1),
+               "v3ks1": (3, 1, -1), "v3ks2": (3, 2, -1)}
+F32_ONE_STEP = {64: [(1, 64), (2, 63), (31, 33), (32, 1)], 32: [(1, 32), (2, 31)], 24: [(1, 24), (2, 23)]}  # one step of that many rows
+F32_STEPS = {64: [(100, 128), (150, 192), (300, 320)], 32: [(50, 64), (80, 96), (150, 160)], 24: [(40, 48), (60, 72), (110, 120)]}  # 2, 3, 5 steps: partial, full
+F32_LEARN = {64: (150, 300), 32: (80, 150), 24: (60, 110)}  # 3 and 5 steps, the last one partial
+F32_LEARN_HP = {"sgd": dict(kind=1, lr=1e-4, momentum=0.0, wd=0.0, nesterov=False), "nesterov_wd": dict(kind=1, lr=1e-4, momentum=0.9, wd=5e-4, nesterov=True)}
+# ((D0, D3), family, test rows of the two peers, case seed: one at which the tying classes 0 and 1 are the maximum of many rows)
+F32_EVAL = [((784, 10), "exact", (517, 70), 0), ((40, 16), "exact_tie", (1, 512), 2), ((792, 16), "exact_tie", (517, 1), 1), ((8, 1), "exact", (70, 512), 0)]
+
+
+def f32_layout_cases():
+    """``(layout, shape)``: every layout at the main and at the ragged shape, every shape on the shipping layout."""
+    return [(l, s) for l in F32_LAYOUTS for s in (F32_MAIN, F32_RAGGED)] + [("v1ks1", s) for s in F32_SHAPES[2:]]
+
+
+def epoch_perm32(n, ep, p, seed=0):
+    """The pinned epoch order of peer ``p`` in the fp32 oracle tests."""
+    return torch.randperm(n, generator=torch.Generator().manual_seed(1000 * ep + 10 * seed + p)).numpy()
+
+
+def dims32(D0, D3):
+    return (D0, PD1, PD2, D3)
+
+
+def f32_family(D3):
+    """The grid family of a training case: with 16 classes the one whose classes 0 and 1 tie in every row."""
+    return "exact_tie" if D3 == 16 else "exact"
+
+
+def learn_refs(c, p, hp, epochs=1):
+    """Part (d): peer ``p``'s float64 epoch(s) under the pinned orders and the fp32 twin's: ``(ref, alt)``."""
+    out = []
+    for kw in (dict(), dict(mm=mm32_permuted(torch.Generator().manual_seed(p)), f32=True)):
+        W, st = c["W"][p], None
+        for ep in range(epochs):
+            W, st = epoch(W, c["x"][p], c["y"][p], epoch_perm32(c["n"][p], ep, p), c["B"], hp, rnd=ident, state=st, **kw)
+        out.append(W)
+    return out
+
+
+def case32(D0, D3, B, family, n, n_test=(4, 4), seed=0):
+    """2 peers of the fp32 engine with their own weights (peers 0 and 1 of :func:`_weights`) and data: ``n[p]``
+    training rows and ``n_test[p]`` test rows of the family's pixels, labels uniform in ``[0, D3)``."""
+    D = dims32(D0, D3)
+    g = torch.Generator().manual_seed(7 + 1000003 * seed + 7919 * D0 + 5 * D3 + B + 131 * n[0] + 257 * n[1] + 17 * sum(n_test) + sum(map(ord, family)))
+    W = _weights(g, D, "randn" if family == "randn32" else family)
+    if family == "randn32":
+        W = {k: v * RANDN32_SCALE[k] for k, v in W.items()}
+        family = "randn"
+    c = dict(D=D, B=B, family=family, n=list(n), n_test=list(n_test), W=[{k: v[p] for k, v in W.items()} for p in range(2)])
+    c["x"] = [_pixels(g, family, n[p], D0) for p in range(2)]
+    c["y"] = [torch.randint(0, D3, (n[p],), generator=g) for p in range(2)]
+    c["xt"] = [_pixels(g, family, n_test[p], D0) for p in range(2)]
+    c["yt"] = [torch.randint(0, D3, (n_test[p],), generator=g) for p in range(2)]
+    return c
+
+
+def forward32(W, X):
+    H1 = fc(X, W["W1"], W["b1"], ident)
+    H2 = fc(H1, W["W2"], W["b2"], ident)
+    return H1, H2, logits(H2, W["W3"], W["b3"])
+
+
+def grid_ratios(W, X, D):
+    """``sum |term| / unit`` of the worst fc1, fc2 and fc3 sum of the rows ``X`` on ``units(D)``'s grid (and an assertion that
+    every sum lies on it): all three below 2^24 make the fp32 forward exact in any order."""
+    u = units(D)
+    H1, H2, _ = forward32(W, X)
+    out = []
+    for A, w, b, unit in ((X, W["W1"], W["b1"], u[0]), (H1, W["W2"], W["b2"], u[0] * u[1]), (H2, W["W3"], W["b3"], u[0] * u[1] * u[2])):
+        pre = fc_pre(A, w, b)[0]
+        assert torch.equal(pre / unit, (pre / unit).round()), "a sum off its grid"
+        out.append(float(exactness(A, w, b, unit).max()) if A.shape[0] else 0.0)
+    return out
+
+
+def split3(x):
+    """``split3`` of mlp_f32_common.h on float64 values of fp32 numbers: ``(hi, mid, lo)``, bf16 each, ``hi + mid + lo == x``."""
+    hi = bf16(x)
+    r = x - hi
+    mid = bf16(r)
+    return hi, mid, bf16(r - mid)
+
+
+def h2_l3(H1, W2, b2):
+    """Layout 3's H2 before the relu, in exact arithmetic: six of the nine cross terms of the two splits."""
+    ah, am, al = split3(H1)
+    bh, bm, bl = split3(W2)
+    return al @ bh.t() + ah @ bl.t() + am @ bm.t() + am @ bh.t() + ah @ bm.t() + ah @ bh.t() + b2
+
+
+def h2_l3_bound(H1, W2, b2):
+    """``|H2 of layout 3 - relu(H1 W2^T + b2)|`` for arbitrary fp32 operands: the dropped cross terms, 6 * 256 exact
+    products summed in fp32 in some order, and the bias addition."""
+    mag = H1.abs() @ W2.abs().t()
+    return SECOND * ((L3_DROP + gamma(6 * PD1) * (1 + 2.0 ** -7)) * mag + U * (mag + b2.abs()))
+
+
+def eps_softmax32(z):
+    """``(eps_lp, eps_dl)`` of the section comment for the logits ``z`` (the worst row)."""
+    if z.numel() == 0:
+        return 0.0, 0.0
+    eps_lp = eps_softmax(z)[0]
+    rng = float((z.amax(1) - z.amin(1)).max())
+    a = 2 * U * (1 + rng) + U * rng
+    return eps_lp, max(2 * a + 12 * U, eps_lp + 7 * U)
+
+
+def step32(W, X, y):
+    """One step of one peer in float64: the stage tensors, the loss terms, the predictions (first maximum), the six
+    gradients, and ``eps_lp`` / ``eps_dl`` of its logits. ``dlog`` is ``[rows, D3]``."""
+    D3 = W["b3"].shape[0]
+    rows = X.shape[0]
+    H1, H2, z = forward32(W, X)
+    loss, pred, _ = head(z, y)
+    dl = dlogits(z, y, rnd=ident)[:, :D3]
+    dH2 = dgrad(dl, W["W3"], H2, ident)
+    dH1 = dgrad(dH2, W["W2"], H1, ident)
+    pad = torch.zeros(rows, 16, dtype=F64)
+    pad[:, :D3] = dl
+    s = dict(X=X, y=y, rows=rows, H1=H1, H2=H2, z=z, loss=loss, pred=pred, dlog=dl, dH2=dH2, dH1=dH1)
+    s["g"] = wgrads(X, H1, H2, dH1, dH2, pad, D3)
+    s["eps_lp"], s["eps_dl"] = eps_softmax32(z)
+    return s
+
+
+def bounds32(s, W):
+    """The per-element bounds of the six gradients of :func:`step32`'s step (section comment, "Backward")."""
+    rows, X, H1, H2 = s["rows"], s["X"], s["H1"], s["H2"]
+    dl, dH2, dH1 = s["dlog"].abs(), s["dH2"].abs(), s["dH1"].abs()
+    W3a, W2a = W["W3"].abs(), W["W2"].abs()
+    e_dl = s["eps_dl"] / rows
+    e_dH2 = (H2 > 0) * (gamma(16) * (dl @ W3a) + e_dl * W3a.sum(0)[None, :])
+    e_dH1 = (H1 > 0) * (gamma(PD2) * (dH2 @ W2a) + e_dH2 @ W2a)
+    gw, g1 = gamma(rows), (gamma(3 * rows) + 12 * U) * (1 + 2.0 ** -7)
+    b = {
+        "W3": gw * (dl.t() @ H2) + e_dl * H2.sum(0)[None, :].expand(dl.shape[1], -1),
+        "b3": gw * dl.sum(0) + rows * e_dl,
+        "W2": gw * (dH2.t() @ H1) + e_dH2.t() @ H1,
+        "b2": gw * dH2.sum(0) + e_dH2.sum(0),
+        "W1": g1 * (dH1.t() @ X) + e_dH1.t() @ X,
+        "b1": g1 * dH1.sum(0) + e_dH1.sum(0),
+    }
+    return {k: SECOND * v for k, v in b.items()}
+
+
+def outer32(d, a):
+    """``fp32(d[i] * a[j])``: the exact product of two fp32 vectors (48 bits: exact in float64), rounded once."""
+    return (d[:, None] * a[None, :]).float().double()
+
+
+def loss_bound(losses, eps_lp):
+    """Bound of the fp32 sum of the rows' loss terms (any tree) against their float64 sum."""
+    n = losses.numel()
+    return SECOND * (n * eps_lp + gamma(max(n, 1)) * float(losses.abs().sum()))
+
+
+def moments32(hp, w, gs, bs, k0=0):
+    """The moments after ``upd32`` steps on the gradients ``gs`` (each known to its ``bs``) with the weights frozen (``lr = 0``, no
+    weight decay), from zero moments, the first step being optimizer step ``k0 + 1``: ``(m, v, bm, bv)``. Each step's bound
+    is :func:`upd32`'s plus the previous step's carried through the recursion's own factor (beta1 / beta2, or the
+    momentum)."""
+    assert R.f32(hp["lr"]) == 0.0 and hp.get("wd", 0.0) == 0.0
+    m, v = torch.zeros_like(w), torch.zeros_like(w)
+    bm, bv = torch.zeros_like(w), torch.zeros_like(w)
+    cm, cv = (R.f32(BETA1), R.f32(BETA2)) if hp["kind"] == 0 else (R.f32(hp["momentum"]), 0.0)
+    for i, (g, b) in enumerate(zip(gs, bs)):
+        w1, m, v, _, bm1, bv1 = upd32(hp, w, g, m, v, k0 + i + 1, dg=b)
+        assert torch.equal(w1, w)
+        bm, bv = bm1 + cm * bm, bv1 + cv * bv
+    return m, v, bm, bv
+
+
+def _hp32(hp):
+    return {k: (R.f32(v) if isinstance(v, float) else v) for k, v in hp.items()}
+
+
+def adam_coeffs(hp, k):
+    """``(lr_t, inv)`` of ``persist::BiasCorr`` at optimizer step ``k`` (from 1): formed in double from the fp32 betas,
+    rounded to fp32."""
+    b1, b2 = R.f32(BETA1), R.f32(BETA2)
+    return R.f32(R.f32(hp["lr"]) / (1.0 - b1 ** k)), R.f32(1.0 / math.sqrt(1.0 - b2 ** k))
+
+
+def adam_w32(hp, w, m1, v1, k, bm=0.0, bv=0.0):
+    """The weight after ``upd32``'s Adam tail from the new moments ``m1``, ``v1`` (known to ``bm``, ``bv``) at step ``k``:
+    ``(w', bound)``."""
+    lr_t, inv = adam_coeffs(hp, k)
+    eps = R.f32(EPS)
+    sq = torch.sqrt(v1)
+    d_sq = 2 * U * sq + torch.minimum(torch.sqrt(torch.as_tensor(bv, dtype=F64) + 0 * sq), torch.as_tensor(bv, dtype=F64) / sq.clamp_min(1e-300)) + 2.0 ** -60
+    den = sq * inv + eps
+    d_den = inv * d_sq + 2 * U * sq * inv + U * den
+    q = m1 / den
+    dq = bm / den + q.abs() * (d_den / den + 3 * U)
+    w1 = w - lr_t * q
+    return w1, SECOND * (U * w1.abs() + lr_t * dq + 2 * U * lr_t * q.abs())
+
+
+def upd32(hp, w, g, m, v, k, anchor=None, cg=None, cl=None, dg=0.0):
+    """``upd32`` of mlp_f32_common.h on float64 values of the kernel's fp32 inputs (``g`` known to ``dg``): one step, ``k``
+    the optimizer step from 1. ``hp``: an ``OPT_VARIANTS`` entry (``mu`` with ``anchor``: FedProx; ``cg`` / ``cl``: SCAFFOLD in
+    update space). Returns ``(w', m', v', bw, bm, bv)``, the bounds absolute (section comment); ``m'`` is ``m`` where the
+    variant leaves it alone, ``v'`` is ``v`` under SGD."""
+    hp = _hp32(hp)
+    wdmu = R.f32(hp.get("wd", 0.0) + (hp.get("mu", 0.0) if anchor is not None else 0.0))
+    zero = torch.zeros_like(w)
+    dg = dg + zero
+    if wdmu != 0.0:
+        g = g + wdmu * w
+        dg = dg + U * g.abs()
+    if anchor is not None:
+        e = -hp["mu"] * anchor
+        g = g + e
+        dg = dg + U * e.abs() + U * g.abs()
+    if hp["kind"] == 0:
+        b1, b2 = R.f32(BETA1), R.f32(BETA2)
+        m1 = b1 * m + (1.0 - b1) * g
+        bm = U * m1.abs() + (1.0 - b1) * (U * g.abs() + dg)
+        v1 = b2 * v + (1.0 - b2) * g * g
+        bv = U * v1 + (1.0 - b2) * (2 * U * g * g + 2 * g.abs() * dg)
+        w1, bw = adam_w32(hp, w, m1, v1, k, bm, bv)
+        bm, bv = SECOND * bm, SECOND * bv
+    else:
+        mom, lr = hp.get("momentum", 0.0), hp["lr"]
+        m1, v1, bm, bv = m, v, zero, zero
+        gu, dgu = g, dg
+        if mom != 0.0:
+            m1 = mom * m + g
+            bm = U * m1.abs() + dg
+            gu, dgu = m1, bm
+            if hp.get("nesterov", False):
+                gu = mom * m1 + g
+                dgu = U * gu.abs() + mom * bm + dg
+            bm = SECOND * bm
+        w1 = w - lr * gu
+        bw = SECOND * (U * w1.abs() + lr * dgu)
+    if cg is not None:
+        e = cg - cl
+        w1 = w1 - hp["lr"] * e
+        bw = bw + SECOND * (U * w1.abs() + hp["lr"] * U * e.abs())
+    return w1, m1, v1, bw, bm, bv

@@ -208,3 +208,217 @@ def test_exact_evaluation_cases(D, family, n_test, active):
                 assert D[3] == 1 or not tied.any()
     if family == "exact_tie":
         assert ties > 10
+
+
+# ---------------------------------------------------------------------------------------------
+# the fp32 epoch kernels' oracle (tests/test_mlp_f32_oracle_gpu.py)
+# ---------------------------------------------------------------------------------------------
+def _f32_grid_cases():
+    out = []
+    for D0, D3, B in M.F32_SHAPES:
+        out += [(D0, D3, B, n) for n in M.F32_ONE_STEP[B] + M.F32_STEPS[B]]
+    return out
+
+
+@pytest.mark.parametrize("D0,D3,B,n", _f32_grid_cases(), ids=lambda v: "-".join(map(str, v)) if isinstance(v, tuple) else str(v))
+def test_f32_grid_training_cases_are_exact(D0, D3, B, n):
+    """Every training case of parts (a), (b) and (c): all rows of both peers, H1 and H2 NOT rounded (the fp32 kernel
+    keeps them in fp32): ``sum |term| / unit < 2^24`` at fc1, fc2 and fc3, every value an fp32 number. With D3 = 16 the
+    family is ``exact_tie``: classes 0 and 1 tie in every row."""
+    c = M.case32(D0, D3, B, M.f32_family(D3), n)
+    for p in range(2):
+        W, X = c["W"][p], c["x"][p].double()
+        assert all(torch.equal(v.float().double(), v) for v in W.values())
+        r = M.grid_ratios(W, X, c["D"])
+        H1, H2, z = M.forward32(W, X)
+        assert all(torch.equal(t.float().double(), t) for t in (H1, H2, z))
+        assert max(r) < M.LIM, r
+        if D3 == 16:
+            assert torch.equal(z[:, 0], z[:, 1])
+        if X.shape[0] > 8:
+            assert (H1 > 0).any() and (H1 == 0).any() and (H2 > 0).any() and (H2 == 0).any()
+    print("sum |term| / unit / 2^24: fc1 %.2e, fc2 %.2e, fc3 %.2e" % tuple(x / M.LIM for x in r))
+
+
+@pytest.mark.parametrize("D,family,n_test,seed", M.F32_EVAL, ids=[f"{c[0][0]}-{c[1]}" for c in M.F32_EVAL])
+def test_f32_grid_evaluation_cases_are_exact(D, family, n_test, seed):
+    """The test rows of part (e): exact at fc1, fc2 and fc3, and in the tie family more than 10 rows whose maximum is
+    shared by classes 0 and 1."""
+    c = M.case32(D[0], D[1], 64, family, (4, 4), n_test, seed)
+    ties = 0
+    for p in range(2):
+        X = c["xt"][p].double()
+        assert max(M.grid_ratios(c["W"][p], X, c["D"])) < M.LIM
+        z = M.forward32(c["W"][p], X)[2]
+        ties += int(((z == z.amax(1, keepdim=True)).sum(1) > 1).sum())
+    assert family != "exact_tie" or ties > 10
+
+
+def _torch_mlp(W, D):
+    from myfyp_amd.models import MLP
+
+    m = MLP(input_size=D[0], hidden_sizes=[D[1], D[2]], out_channels=D[3]).double()
+    with torch.no_grad():
+        for i, l in enumerate(m.linear_layers()):
+            l.weight.copy_(W[f"W{i + 1}"])
+            l.bias.copy_(W[f"b{i + 1}"])
+    return m
+
+
+@pytest.mark.parametrize("name", ["nesterov_wd", "adam"])
+def test_epoch_without_rounding_is_autograd_with_torch_optim(name):
+    """Two epochs of one fit (the moments and the step count carried over), 3 steps each, the last batch partial:
+    float64 autograd + ``torch.optim`` with the fp32 values of the hyperparameters."""
+    f = M.R.f32
+    hp = M.F32_LEARN_HP["nesterov_wd"] if name == "nesterov_wd" else dict(kind=0, lr=1e-3, wd=1e-4)
+    c = M.case32(40, 10, 24, "randn32", (60, 60))
+    W, x, y = c["W"][0], c["x"][0], c["y"][0]
+    perms = [M.epoch_perm32(60, ep, 0) for ep in range(2)]
+    got, st = M.epoch(W, x, y, perms[0], 24, hp, rnd=M.ident)
+    got, st = M.epoch(got, x, y, perms[1], 24, hp, rnd=M.ident, state=st)
+    assert st[2] == 6
+    m = _torch_mlp(W, c["D"])
+    if name == "adam":
+        opt = torch.optim.Adam(m.parameters(), lr=f(hp["lr"]), betas=(f(M.BETA1), f(M.BETA2)), eps=f(M.EPS), weight_decay=f(hp["wd"]))
+    else:
+        opt = torch.optim.SGD(m.parameters(), lr=f(hp["lr"]), momentum=f(hp["momentum"]), weight_decay=f(hp["wd"]), nesterov=True)
+    for perm in perms:
+        for s in range(0, 60, 24):
+            idx = torch.as_tensor(perm[s: s + 24])
+            h = x[idx].double()
+            for layer in m.layers:
+                h = layer(h)
+            opt.zero_grad()
+            F.cross_entropy(h, y[idx].long()).backward()
+            opt.step()
+    for i, l in enumerate(m.linear_layers()):
+        for k, want in ((f"W{i + 1}", l.weight), (f"b{i + 1}", l.bias)):
+            upd = float((want.detach() - W[k]).abs().max())
+            assert upd > 0 and float((got[k] - want.detach()).abs().max()) <= 1e-9 * upd, k
+
+
+def test_sgd_epoch_is_the_plain_sgd_epoch():
+    c = M.case32(40, 10, 24, "randn32", (60, 60))
+    perm = M.epoch_perm32(60, 0, 0)
+    a = M.sgd_epoch(c["W"][0], c["x"][0], c["y"][0], perm, 24, 1e-2)
+    b = M.epoch(c["W"][0], c["x"][0], c["y"][0], perm, 24, dict(kind=1, lr=1e-2, momentum=0.0, wd=0.0, nesterov=False))[0]
+    assert all(torch.equal(a[k], b[k]) for k in M.NAMES) and not torch.equal(a["W1"], c["W"][0]["W1"])
+
+
+def test_split3_and_the_cross_terms_layout_3_drops():
+    """``split3`` is exact with ``|mid| <= 2^-8 |x|`` and ``|lo| <= 2^-16 |x|``; the three dropped cross terms reach beyond 2^-26
+    of a product (so neither 2^-32 nor 2^-26 bounds them) and stay within ``L3_DROP``; on the grid they vanish; for random
+    fp32 operands the six-term H2 is within :func:`h2_l3_bound` of the exact one."""
+    g = torch.Generator().manual_seed(3)
+    x = (torch.randn(1 << 16, generator=g) * torch.exp2(torch.randint(-20, 20, (1 << 16,), generator=g).float())).double()
+    hi, mid, lo = M.split3(x)
+    assert torch.equal(hi + mid + lo, x)
+    assert float((mid.abs() / x.abs()).max()) <= 2.0 ** -8 and float((lo.abs() / x.abs()).max()) <= 2.0 ** -16
+    a, b = x[: 1 << 15], x[1 << 15:]
+    (ah, am, al), (bh, bm, bl) = M.split3(a), M.split3(b)
+    drop = ((am * bl + al * bm + al * bl).abs() / (a * b).abs()).max()
+    print(f"largest dropped part of a product: 2^{math.log2(float(drop)):.2f}")
+    assert 2.0 ** -26 < float(drop) <= M.L3_DROP
+    c = M.case32(784, 10, 64, "exact", (64, 64))
+    W = c["W"][0]
+    H1 = M.forward32(W, c["x"][0].double())[0]
+    assert torch.equal(M.h2_l3(H1, W["W2"], W["b2"]), H1 @ W["W2"].t() + W["b2"])
+    H1r = torch.randn(64, 256, generator=g).float().double().clamp_min(0)
+    W2r, b2r = torch.randn(128, 256, generator=g).float().double() / 16, torch.randn(128, generator=g).float().double()
+    err = (M.h2_l3(H1r, W2r, b2r) - (H1r @ W2r.t() + b2r)).abs()
+    assert float(err.max()) > 0 and (err <= M.h2_l3_bound(H1r, W2r, b2r)).all()
+
+
+def _fma(a, b, c):
+    return (a * b + c).float().double()
+
+
+def _r(t):
+    return t.float().double()
+
+
+@pytest.mark.parametrize("D0,D3,B,rows", [(784, 10, 64, 64), (40, 16, 24, 23), (8, 1, 32, 1), (40, 10, 24, 1)])
+def test_f32_emulated_step_stays_inside_the_bounds(D0, D3, B, rows):
+    """One step on the grid with every sum accumulated in fp32 over a permuted reduction axis and the softmax in fp32:
+    the forward is the float64 one bit for bit, the six gradients are within :func:`bounds32`; with one row the weight
+    gradients are :func:`outer32` of the bias gradients."""
+    c = M.case32(D0, D3, B, M.f32_family(D3), (rows, rows))
+    for p in range(2):
+        W, X, y = c["W"][p], c["x"][p].double(), c["y"][p].long()
+        s = M.step32(W, X, y)
+        mm = M.mm32_permuted(torch.Generator().manual_seed(p))
+        H1 = (mm(X, W["W1"].t()) + W["b1"]).float().double().clamp_min(0)
+        H2 = (mm(H1, W["W2"].t()) + W["b2"]).float().double().clamp_min(0)
+        z = (mm(H2, W["W3"].t()) + W["b3"]).float().double()
+        assert torch.equal(H1, s["H1"]) and torch.equal(H2, s["H2"]) and torch.equal(z, s["z"])
+        sm = torch.softmax(z.float(), 1)
+        sm[torch.arange(rows), y] -= 1.0
+        dl = (sm / rows).double()
+        assert float((dl * rows - s["dlog"] * rows).abs().max()) <= s["eps_dl"]
+        zero = torch.zeros((), dtype=F64)
+        dH2 = torch.where(H2 > 0, mm(dl, W["W3"]), zero)
+        dH1 = torch.where(H1 > 0, mm(dH2, W["W2"]), zero)
+        one = torch.ones(rows, 1, dtype=F64)
+        g = {"W1": mm(dH1.t(), X), "b1": mm(dH1.t(), one)[:, 0], "W2": mm(dH2.t(), H1), "b2": mm(dH2.t(), one)[:, 0], "W3": mm(dl.t(), H2), "b3": mm(dl.t(), one)[:, 0]}
+        bnd = M.bounds32(s, W)
+        for k in M.NAMES:
+            err = (g[k] - s["g"][k]).abs()
+            assert (err <= bnd[k]).all(), (k, float((err / bnd[k].clamp_min(1e-300)).max()))
+            # (one batch row missing from a sum moves it by about 1 / rows >= 2^-6 of its size)
+            assert D3 == 1 or float(bnd[k].max()) < 2.0 ** -10 * float(s["g"][k].abs().max()), f"{k}: a bound that says nothing"
+        if rows == 1:
+            for k, b, a in (("W3", "b3", H2), ("W2", "b2", H1), ("W1", "b1", X)):
+                assert torch.equal(g[k], M.outer32(g[b], a[0]))
+
+
+@pytest.mark.parametrize("variant", list(M.OPT_VARIANTS))
+def test_upd32_emulation_stays_inside_its_bounds(variant):
+    """``upd32``'s operation sequence emulated in fp32 (each fma rounded once, sqrt and the reciprocal correctly rounded)
+    against :func:`upd32` in float64, for every optimizer variant, from non-zero moments at step 4."""
+    hp = dict(M.OPT_VARIANTS[variant], t0=3)
+    g = torch.Generator().manual_seed(11)
+    n = 4096
+    w, gr = _r(torch.randn(n, generator=g) * 0.1), _r(torch.randn(n, generator=g) * torch.exp2(torch.randint(-30, 0, (n,), generator=g).float()))
+    m, v = _r(torch.randn(n, generator=g) * 1e-3), _r(torch.rand(n, generator=g) * 1e-6)
+    anchor = _r(w + 0.01 * torch.randn(n, generator=g)) if "mu" in hp else None
+    cg, cl = (_r(torch.randn(n, generator=g) * 1e-3), _r(torch.randn(n, generator=g) * 1e-3)) if hp.get("scaffold") else (None, None)
+    k = 4
+    w1, m1, v1, bw, bm, bv = M.upd32(hp, w, gr, m, v, k, anchor, cg, cl)
+    h = M._hp32(hp)
+    wdmu = M.R.f32(h.get("wd", 0.0) + (h.get("mu", 0.0) if anchor is not None else 0.0))
+    ge = _fma(torch.full_like(w, wdmu), w, gr)
+    if anchor is not None:
+        ge = _r(ge + _r(-h["mu"] * anchor))
+    if hp["kind"] == 0:
+        b1, b2 = M.R.f32(M.BETA1), M.R.f32(M.BETA2)
+        lr_t, inv = M.adam_coeffs(hp, k)
+        me = _fma(torch.full_like(w, b1), m, _r((1.0 - b1) * ge))
+        ve = _fma(torch.full_like(w, b2), v, _r((1.0 - b2) * _r(ge * ge)))
+        den = _fma(_r(torch.sqrt(ve)), torch.full_like(w, inv), torch.full_like(w, M.R.f32(M.EPS)))
+        we = _fma(torch.full_like(w, -lr_t), _r(me * _r(1.0 / den)), w)
+    else:
+        me, ve, gu = m, v, ge
+        if h["momentum"] != 0.0:
+            me = _fma(torch.full_like(w, h["momentum"]), m, ge)
+            gu = _fma(torch.full_like(w, h["momentum"]), me, ge) if h["nesterov"] else me
+        we = _fma(torch.full_like(w, -h["lr"]), gu, w)
+    if cg is not None:
+        we = _fma(torch.full_like(w, -h["lr"]), _r(cg - cl), we)
+    for name, got, want, b in (("w", we, w1, bw), ("m", me, m1, bm), ("v", ve, v1, bv)):
+        err = (got - want).abs()
+        assert (err <= b).all(), (name, float((err / b.clamp_min(1e-300)).max()))
+    assert not torch.equal(we, w) and float((bw / w1.abs().clamp_min(1e-30)).median()) < 2.0 ** -20
+
+
+@pytest.mark.parametrize("hp", list(M.F32_LEARN_HP))
+@pytest.mark.parametrize("shape", [M.F32_MAIN, M.F32_RAGGED], ids=["main", "ragged"])
+def test_f32_learning_cases_are_not_chaotic(shape, hp):
+    """Part (d)'s cases: the twin's floor (fp32 sums in another order, fp32 optimizer and master row, against the
+    float64 epoch) is below 1e-4 for every tensor of both peers, so 8 times it still sees a single stale step."""
+    D0, D3, B = shape
+    c = M.case32(D0, D3, B, "randn32", M.F32_LEARN[B])
+    for p in range(2):
+        ref, alt = M.learn_refs(c, p, M.F32_LEARN_HP[hp])
+        floors = {k: M.rel_update(alt[k], ref[k], c["W"][p][k]) for k in M.NAMES}
+        print(f"peer {p}: " + ", ".join(f"{k} {v:.2e}" for k, v in floors.items()))
+        assert 0 < max(floors.values()) < 1e-4, floors
