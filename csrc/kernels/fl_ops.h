@@ -79,6 +79,28 @@ void fl_bulyan(float* work, const OutPtrs& outs, int P, const RowPtrs& rows, int
                float* coef, hipStream_t s);
 // The last of fl_bulyan's launches alone: coef[K] in device memory marks the K - 2f picked rows.
 void fl_bulyan_mean(const OutPtrs& outs, int P, const RowPtrs& rows, int K, int f, const float* coef, int64_t n, hipStream_t s);
+// ClippedGossip (He, Karimireddy, Jaggi, 2022) of rows 0..K-1 in place: row p moves towards each
+// neighbour q (w[p][q] > 0, q != p; the diagonal is ignored) by at most a radius,
+//   x_p <- x_p + sum_q w_eff[p][q] (x_q - x_p),  w_eff[p][q] = float(w[p][q] * min(1, tau_p / |x_q - x_p|)).
+// mode CLIP_FIXED: tau_p = tau. mode CLIP_ADAPTIVE: the min(b, |N_p|) farthest neighbours F_p (a
+// non-finite distance counts as +inf, here and in the sum below; among equals the higher row is
+// farther) are set aside and tau_p^2 = sum_{N_p \ F_p} w[p][q] D_pq / sum_{F_p} w[p][q]; b == 0:
+// tau_p = +inf (plain mixing), F_p == N_p: tau_p = 0. A neighbour at a non-finite distance gets
+// w_eff 0, and rows of w_eff 0 never enter a sum: a NaN row reaches nobody and is itself left as it
+// is; a row p whose w[p][.] is all zero is a source only and is never written. Distances as
+// fl_krum_select's, on the same grid (work holds the same floats). Device outputs dist[K*K],
+// tau[K] (double) and w_eff[K*K] (float). Three launches (none for K == 1); every thread loads its
+// coordinates of all rows before it stores, so the update is in-place safe.
+#define CLIP_FIXED 0
+#define CLIP_ADAPTIVE 1
+struct ClipPlan {
+  float w[16][16];
+  double tau;
+  int mode;
+  int b;
+};
+void fl_clipped_gossip(float* work, const OutPtrs& rows, int K, const ClipPlan& plan, int64_t n, double* dist, double* tau, float* w_eff,
+                       hipStream_t s);
 // Colluding attacks: one crafted row m from the K honest rows 0..K-1, stored into out rows 0..P-1
 // (which are not among the rows). kind: 0 ALIE, 1 IPM, 2 min-max, 3 min-sum. m = ca·μ + cb·σ + cr·ref
 // per coordinate (μ, σ: mean and population standard deviation of the honest values). ALIE and IPM

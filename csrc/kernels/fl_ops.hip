@@ -579,6 +579,112 @@ __global__ __launch_bounds__(FL_BLOCK) void k_coef_mean(OutPtrs outs, int P, Row
   }
 }
 
+// ClippedGossip (He, Karimireddy, Jaggi, 2022) in three launches: k_pairwise_sqdist<K> on Krum's
+// grid, then
+//   k_clip_plan        : one block sums the slabs as k_krum_select does; thread p forms row p's
+//                        radius and the clipped weights of its neighbours in double
+//   k_clipped_mix<K>   : x_p <- x_p + Σ_q w_eff[p][q] (x_q − x_p) in place
+// Row p's neighbours N_p are the q != p with w[p][q] > 0. Adaptive radius: the min(b, |N_p|)
+// farthest neighbours F_p are set aside (a non-finite distance counts as +inf, the higher row is
+// the farther of two equals) and τ_p² = Σ_{N_p∖F_p} w_pq D_pq / Σ_{F_p} w_pq, both sums in ascending
+// q; b == 0: τ_p = +inf, F_p == N_p: τ_p = 0. Scale: 0 at a non-finite distance, 1 where D_pq <= τ_p²,
+// else τ_p / sqrt(D_pq); w_eff[p][q] = float(w_pq · scale), rounded once.
+__global__ __launch_bounds__(KRUM_SELECT_BLOCK) void k_clip_plan(const float* __restrict__ work, int G, int K, ClipPlan plan,
+                                                                 double* __restrict__ dist, double* __restrict__ tau, float* __restrict__ w_eff) {
+  __shared__ double d[16][16];
+  __shared__ float wsh[16][16];
+  __shared__ double part[KRUM_SELECT_BLOCK];
+  const int t = threadIdx.x;
+  if (t < 256) wsh[t / 16][t % 16] = plan.w[t / 16][t % 16];
+  krum_sum_slabs(work, G, K, d, part);  // ends with a barrier: wsh is visible too
+  for (int q = t; q < K * K; q += KRUM_SELECT_BLOCK) dist[q] = d[q / K][q % K];
+  if (t < K) {
+    const double inf = __builtin_huge_val();
+    unsigned nb = 0;
+    int cnt = 0;
+    for (int q = 0; q < K; ++q) {
+      if (q != t && wsh[t][q] > 0.f) {
+        nb |= 1u << q;
+        ++cnt;
+      }
+    }
+    double tp, tp2;
+    if (plan.mode == CLIP_FIXED) {
+      tp = plan.tau;
+      tp2 = tp * tp;
+    } else if (plan.b == 0) {
+      tp = tp2 = inf;
+    } else if (plan.b >= cnt) {
+      tp = tp2 = 0.0;
+    } else {
+      double delta = 0.0, sum = 0.0;
+      for (int q = 0; q < K; ++q) {
+        if (!((nb >> q) & 1u)) continue;
+        const double kq = __builtin_isfinite(d[t][q]) ? d[t][q] : inf;
+        int rank = 0;  // neighbours farther than q
+        for (int r = 0; r < K; ++r) {
+          if (r == q || !((nb >> r) & 1u)) continue;
+          const double kr = __builtin_isfinite(d[t][r]) ? d[t][r] : inf;
+          if (kr > kq || (kr == kq && r > q)) ++rank;
+        }
+        if (rank < plan.b) delta += (double)wsh[t][q];
+        else sum += (double)wsh[t][q] * kq;
+      }
+      tp2 = sum / delta;
+      tp = sqrt(tp2);
+    }
+    tau[t] = tp;
+    for (int q = 0; q < K; ++q) {
+      float e = 0.f;
+      const double D = d[t][q];
+      if (((nb >> q) & 1u) && __builtin_isfinite(D)) {
+        const double scale = D <= tp2 ? 1.0 : tp / sqrt(D);
+        e = (float)((double)wsh[t][q] * scale);
+      }
+      w_eff[t * K + q] = e;
+    }
+  }
+}
+
+// One thread owns four consecutive coordinates of every row: it loads them from all K rows, then
+// stores each written row p, so the in-place update never reads a value another thread has
+// written. Per coordinate acc <- fma(w_eff[p][q], x_q − x_p, acc) over q ascending from 0, then
+// x_p + acc, all in fp32; a q of w_eff 0 never enters the sum (a NaN row reaches nobody) and a row
+// whose w_eff are all 0 is not stored. w_eff is wave-uniform: every branch on it is a scalar one,
+// and every register index is static.
+template <int K, bool VEC>
+__global__ __launch_bounds__(FL_BLOCK) void k_clipped_mix(OutPtrs rows, const float* __restrict__ w_eff, int64_t n) {
+  const int64_t groups = (n + 3) / 4;
+  const int64_t stride = (int64_t)gridDim.x * FL_BLOCK;
+  for (int64_t g = (int64_t)blockIdx.x * FL_BLOCK + threadIdx.x; g < groups; g += stride) {
+    float4 v[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = load4<VEC>(rows.p[k], g, n);
+#pragma unroll
+    for (int p = 0; p < K; ++p) {
+      float4 acc = {0.f, 0.f, 0.f, 0.f};
+      bool any = false;
+      // row p's weights are fetched here, K scalars at a time: hoisted out of the loops, the K·K
+      // of them would not fit the scalar registers
+      const float* wl = w_eff + p * K;
+      asm volatile("" : "+s"(wl));
+      const __attribute__((address_space(4))) float* wp = (const __attribute__((address_space(4))) float*)wl;
+#pragma unroll
+      for (int q = 0; q < K; ++q) {
+        if (q == p) continue;
+        const float e = wp[q];
+        if (e == 0.f) continue;
+        any = true;
+        acc.x = fmaf(e, v[q].x - v[p].x, acc.x); acc.y = fmaf(e, v[q].y - v[p].y, acc.y);
+        acc.z = fmaf(e, v[q].z - v[p].z, acc.z); acc.w = fmaf(e, v[q].w - v[p].w, acc.w);
+      }
+      if (!any) continue;
+      const float4 o = {v[p].x + acc.x, v[p].y + acc.y, v[p].z + acc.z, v[p].w + acc.w};
+      store4<VEC>(rows.p[p], g, n, o);
+    }
+  }
+}
+
 // Bulyan (El Mhamdi, Guerraoui, Rouault, 2018) in three launches: k_pairwise_sqdist<K> on Krum's
 // grid, then
 //   k_bulyan_select    : one block sums the slabs as k_krum_select does and picks θ = K − 2f rows by
@@ -1249,6 +1355,27 @@ void fl_coef_mean(const OutPtrs& outs, int P, const RowPtrs& rows, int K, const 
     COEF_CASE(1) COEF_CASE(2) COEF_CASE(3) COEF_CASE(4) COEF_CASE(5) COEF_CASE(6) COEF_CASE(7) COEF_CASE(8)
     COEF_CASE(9) COEF_CASE(10) COEF_CASE(11) COEF_CASE(12) COEF_CASE(13) COEF_CASE(14) COEF_CASE(15) COEF_CASE(16)
 #undef COEF_CASE
+    default: break;
+  }
+}
+void fl_clipped_gossip(float* work, const OutPtrs& rows, int K, const ClipPlan& plan, int64_t n, double* dist, double* tau, float* w_eff,
+                       hipStream_t s) {
+  if (K < 2 || K > 16) return;  // one row has no neighbour
+  RowPtrs src{};
+  for (int k = 0; k < K; ++k) src.p[k] = rows.p[k];
+  const unsigned grid = launch_pairwise_sqdist(work, src, K, n, s);
+  hipLaunchKernelGGL(k_clip_plan, dim3(1), dim3(KRUM_SELECT_BLOCK), 0, s, work, (int)grid, K, plan, dist, tau, w_eff);
+  const bool vec = all_aligned16(src, K, nullptr, 0);
+  const dim3 g(grid_for((n + 3) / 4)), b(FL_BLOCK);
+  switch (K) {
+#define CLIP_CASE(KK)                                                                  \
+  case KK:                                                                             \
+    if (vec) hipLaunchKernelGGL((k_clipped_mix<KK, true>), g, b, 0, s, rows, w_eff, n); \
+    else hipLaunchKernelGGL((k_clipped_mix<KK, false>), g, b, 0, s, rows, w_eff, n);    \
+    break;
+    CLIP_CASE(2) CLIP_CASE(3) CLIP_CASE(4) CLIP_CASE(5) CLIP_CASE(6) CLIP_CASE(7) CLIP_CASE(8)
+    CLIP_CASE(9) CLIP_CASE(10) CLIP_CASE(11) CLIP_CASE(12) CLIP_CASE(13) CLIP_CASE(14) CLIP_CASE(15) CLIP_CASE(16)
+#undef CLIP_CASE
     default: break;
   }
 }

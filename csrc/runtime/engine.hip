@@ -1040,6 +1040,42 @@ int myfyp_krum_multi(const uint64_t* outs, int P, const uint64_t* srcs, const fl
   }
   return 0;
 }
+// ClippedGossip of rows 0..K-1 in place (fl_clipped_gossip): W_host is the dense [K][K] matrix of
+// the shares row p gives its neighbours (>= 0, the diagonal ignored, an all-zero row is a source
+// only); mode 0: the fixed radius tau, mode 1: the adaptive radius for at most b hostile neighbours.
+// Device outputs dist[K*K], tau_out[K] (double) and w_eff[K*K] (float). work: myfyp_krum_grid(n, K) *
+// K(K-1)/2 floats. Enqueues three launches; K == 1 launches nothing and writes no output.
+int myfyp_clipped_gossip(const uint64_t* rows, int K, const float* W_host, int mode, double tau, int b, int64_t n, float* work, double* dist,
+                         double* tau_out, float* w_eff, void* stream) {
+  if (!rows_ok(K, "clipped_gossip")) return 2;
+  if (n < 1 || rows == nullptr || W_host == nullptr || dist == nullptr || tau_out == nullptr || w_eff == nullptr || (K > 1 && work == nullptr)) {
+    g_last_error = "clipped_gossip: n >= 1 and the row table, W and the work / dist / tau / w_eff buffers are required";
+    return 2;
+  }
+  if ((mode != CLIP_FIXED && mode != CLIP_ADAPTIVE) || (mode == CLIP_FIXED && !(tau >= 0.0)) || (mode == CLIP_ADAPTIVE && b < 0)) {
+    g_last_error = "clipped_gossip: mode 0 takes a radius tau >= 0, mode 1 a bound b >= 0";
+    return 2;
+  }
+  ClipPlan plan{};
+  OutPtrs r{};
+  for (int p = 0; p < K; ++p) {
+    r.p[p] = reinterpret_cast<float*>(rows[p]);
+    for (int q = 0; q < K; ++q) {
+      const float wq = W_host[p * K + q];
+      if (!(wq >= 0.f) || wq - wq != 0.f) {
+        g_last_error = "clipped_gossip: weights are finite and >= 0";
+        return 2;
+      }
+      plan.w[p][q] = wq;
+    }
+  }
+  plan.mode = mode;
+  plan.tau = tau;
+  plan.b = b;
+  fl_clipped_gossip(work, r, K, plan, n, dist, tau_out, w_eff, (hipStream_t)stream);
+  CHECK_HIP(hipGetLastError());
+  return 0;
+}
 static bool bulyan_ok(int K, int P, int f, int64_t n) {
   if (!rows_ok(K, "bulyan") || (P != 0 && !rows_ok(P, "bulyan outputs"))) return false;
   if (f < 0 || (f > 0 && K < 4 * f + 3)) {

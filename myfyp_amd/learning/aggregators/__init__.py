@@ -1,7 +1,8 @@
-"""Aggregators: FedAvg, FedMedian, SCAFFOLD, FedProx, robust (Krum, trimmed mean, geometric median, Bulyan), decentralised NeighborAvg."""
+"""Aggregators: FedAvg, FedMedian, SCAFFOLD, FedProx, robust (Krum, trimmed mean, geometric median, Bulyan), decentralised NeighborAvg and its robust form ClippedGossip."""
 
 from myfyp_amd.learning.aggregators.aggregator import Aggregator, NoModelsToAggregateError
 from myfyp_amd.learning.aggregators.bulyan import Bulyan
+from myfyp_amd.learning.aggregators.clipped_gossip import ClippedGossip
 from myfyp_amd.learning.aggregators.fedavg import FedAvg
 from myfyp_amd.learning.aggregators.fedmedian import FedMedian
 from myfyp_amd.learning.aggregators.fedprox import FedProx
@@ -11,4 +12,4 @@ from myfyp_amd.learning.aggregators.neighbor_avg import NeighborAvg
 from myfyp_amd.learning.aggregators.scaffold import Scaffold
 from myfyp_amd.learning.aggregators.trimmed_mean import TrimmedMean
 
-__all__ = ["Aggregator", "NoModelsToAggregateError", "Bulyan", "FedAvg", "FedMedian", "FedProx", "GeometricMedian", "Krum", "NeighborAvg", "Scaffold", "TrimmedMean"]
+__all__ = ["Aggregator", "NoModelsToAggregateError", "Bulyan", "ClippedGossip", "FedAvg", "FedMedian", "FedProx", "GeometricMedian", "Krum", "NeighborAvg", "Scaffold", "TrimmedMean"]

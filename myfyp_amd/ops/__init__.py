@@ -19,6 +19,9 @@ Ops
 * ``bulyan_into`` — Bulyan: Krum's distances, θ = K − 2f rows picked by iterated Krum, then per
   coordinate the mean of the K − 4f picked values closest to their median, all on the device
   (K ≤ 16); returns ``(dist, score, coef, pick)``
+* ``clipped_gossip_into`` — ClippedGossip: Krum's distances, per row a clipping radius and the
+  clipped neighbour weights, then the mix in place, all on the device (K ≤ 16); returns
+  ``(dist, tau, w_eff)``
 * ``adam_step`` / ``sgd_step`` — fused optimizers over a flat buffer, optionally with the FedProx
   proximal term and the SCAFFOLD control-variate correction fused in (K5, K8, K13)
 * ``scale_add_noise`` — attack injection (sign flip / Gaussian noise, K14)
@@ -45,6 +48,7 @@ __all__ = [
     "krum_into",
     "geometric_median_into",
     "bulyan_into",
+    "clipped_gossip_into",
     "collude_into",
     "alie_z",
     "adam_step",
@@ -268,6 +272,119 @@ def krum_into(rows: Sequence[torch.Tensor], outs: Sequence[torch.Tensor], weight
         for o in outs:
             o.copy_(mean)
     return dist, score, coef
+
+
+def _clip_check(w, k: int, tau, num_byzantine) -> None:
+    """The arguments of a ClippedGossip call, checked before anything is launched or written."""
+    import numpy as np
+
+    if (tau is None) == (num_byzantine is None):
+        raise ValueError("clipped gossip takes exactly one of tau and num_byzantine")
+    if tau is not None and not float(tau) >= 0:
+        raise ValueError(f"clipped gossip: the radius tau must be >= 0, got {tau}")
+    if num_byzantine is not None and (int(num_byzantine) != num_byzantine or num_byzantine < 0):
+        raise ValueError(f"clipped gossip: num_byzantine must be an integer >= 0, got {num_byzantine}")
+    if w.shape != (k, k):
+        raise ValueError(f"clipped gossip: {k} rows but a weight matrix of shape {w.shape}")
+    if not (np.isfinite(w).all() and (w >= 0).all()):
+        raise ValueError("clipped gossip: the weights must be finite and >= 0")
+
+
+def clip_plan(dist, w, tau: Optional[float] = None, num_byzantine: Optional[int] = None):
+    """ClippedGossip's radii and clipped weights from the squared distances ``dist [K, K]`` and the
+    shares ``w [K, K]`` (numpy, float64 math): ``(tau [K] float64, w_eff [K, K] float32)``. Row p's
+    neighbours are the ``q != p`` with ``w[p, q] > 0``. With ``tau`` every radius is ``tau``; with
+    ``num_byzantine = b`` the ``min(b, |N_p|)`` farthest neighbours (a non-finite distance counts as
+    +inf, the higher row is the farther of two equals) are set aside and ``τ_p² = Σ_rest w·D /
+    Σ_aside w`` (``b == 0``: +inf; nobody left: 0). ``w_eff[p, q] = float32(w[p, q] · s)`` with
+    ``s = 1`` where ``D <= τ_p²``, else ``τ_p / sqrt(D)``, and 0 at a non-finite distance."""
+    import numpy as np
+
+    w = np.asarray(w, dtype=np.float64)
+    k = w.shape[0]
+    dist = np.asarray(dist, dtype=np.float64)
+    if dist.shape != (k, k):
+        raise ValueError(f"clipped gossip: w is {w.shape} and dist {dist.shape}, both must be [K, K]")
+    _clip_check(w, k, tau, num_byzantine)
+    taus = np.zeros(k)
+    w_eff = np.zeros((k, k), dtype=np.float32)
+    inf = float("inf")
+    with np.errstate(all="ignore"):
+        for p in range(k):
+            nb = [q for q in range(k) if q != p and w[p, q] > 0]
+            key = {q: float(dist[p, q]) if np.isfinite(dist[p, q]) else inf for q in nb}
+            if tau is not None:
+                tp = float(tau)
+                tp2 = tp * tp
+            elif num_byzantine == 0:
+                tp = tp2 = inf
+            elif num_byzantine >= len(nb):
+                tp = tp2 = 0.0
+            else:
+                aside = set(sorted(nb, key=lambda q: (key[q], q))[len(nb) - int(num_byzantine):])
+                delta = float(sum(w[p, q] for q in nb if q in aside))  # ascending q
+                rest = np.float64(0.0)
+                for q in nb:
+                    if q not in aside:
+                        rest = rest + w[p, q] * key[q]
+                tp2 = float(rest / delta)
+                tp = float(np.sqrt(tp2))
+            taus[p] = tp
+            for q in nb:
+                d = float(dist[p, q])
+                if np.isfinite(d):
+                    w_eff[p, q] = np.float32(w[p, q] * (1.0 if d <= tp2 else tp / np.sqrt(d)))
+    return taus, w_eff
+
+
+def clipped_gossip_into(rows: Sequence[torch.Tensor], w, tau: Optional[float] = None, num_byzantine: Optional[int] = None):
+    """ClippedGossip (He, Karimireddy, Jaggi, 2022) over 1-D fp32 rows, in place: row p moves towards
+    each neighbour by at most its radius, ``x_p ← x_p + Σ_q w_eff[p, q]·(x_q − x_p)`` (q ascending;
+    a q of ``w_eff`` 0 never enters the sum), with the radii and ``w_eff`` of :func:`clip_plan` from
+    the squared distances (from differences) and ``w [K, K]`` taken as float32: ``w[p, q]`` is the
+    share row p gives neighbour q, the diagonal is ignored and a row of zeros marks a source that
+    is never written. Exactly one of ``tau`` (fixed radius) and ``num_byzantine`` (adaptive radius)
+    is given. Returns ``(dist [K, K] float64, tau [K] float64, w_eff [K, K] float32)`` on the rows'
+    device.
+
+    On the GPU (K <= 16 rows) it is three launches — ``k_pairwise_sqdist<K>``, ``k_clip_plan``,
+    ``k_clipped_mix<K>`` — that only enqueue: the host learns the plan when it reads a returned
+    tensor. Elsewhere: float64 torch math (the definition)."""
+    import numpy as np
+
+    k = len(rows)
+    w32 = np.ascontiguousarray(np.asarray(w, dtype=np.float32))
+    _clip_check(w32, k, tau, num_byzantine)
+    dev = rows[0].device
+    if _native_rows(rows, []):
+        lib = _lib()
+        n = rows[0].numel()
+        alloc = torch.zeros if k == 1 else torch.empty  # one row: nothing is launched
+        work = torch.empty(max(1, int(lib.myfyp_krum_grid(n, k)) * (k * (k - 1) // 2)), dtype=torch.float32, device=dev)
+        dist = alloc(k, k, dtype=torch.float64, device=dev)
+        taus = alloc(k, dtype=torch.float64, device=dev)
+        w_eff = alloc(k, k, dtype=torch.float32, device=dev)
+        src, keep_s = _host_ptrs(rows)
+        mode, t, b = (0, float(tau), 0) if tau is not None else (1, 0.0, int(num_byzantine))
+        _native.check(lib.myfyp_clipped_gossip(src, k, w32.ctypes.data, mode, t, b, n, work.data_ptr(), dist.data_ptr(), taus.data_ptr(),
+                                               w_eff.data_ptr(), _stream()), "clipped_gossip")
+        return dist, taus, w_eff
+    x = [r.detach().double() for r in rows]
+    dist = torch.zeros(k, k, dtype=torch.float64, device=dev)
+    for i in range(k):
+        for j in range(i + 1, k):
+            dist[i, j] = dist[j, i] = (x[i] - x[j]).square().sum()
+    taus, w_eff = clip_plan(dist.cpu().numpy(), w32, tau, num_byzantine)
+    with torch.no_grad():
+        for p in range(k):
+            srcs = [q for q in range(k) if w_eff[p, q] != 0]
+            if not srcs:
+                continue
+            acc = torch.zeros_like(x[p])
+            for q in srcs:
+                acc += float(w_eff[p, q]) * (x[q] - x[p])
+            rows[p].copy_(x[p] + acc)
+    return dist, torch.from_numpy(taus).to(dev), torch.from_numpy(w_eff).to(dev)
 
 
 def bulyan_check(k: int, f: int) -> int:

@@ -620,7 +620,9 @@ def aggregate_neighbors(fed: Federation, arrived: Dict[str, Any], aggregator) ->
     """Topology mixing ``x_i ← Σ_j W_ij x_j`` (see ``NeighborAvg``): co-located rows are combined
     with the ``weighted_average`` kernel, rows of neighbours on other ranks arrive through one
     grouped batch of point-to-point sends/receives (RCCL over xGMI; gloo on CPU). Every rank calls
-    this with the same peer list, so the P2P pattern matches by construction."""
+    this with the same peer list, so the P2P pattern matches by construction. A ``ClippedGossip``
+    takes the same sources and exchange, then moves every local row towards each source by at most
+    its radius (``ops.clipped_gossip_into``) and publishes ``last_clipping``."""
     t0 = time.perf_counter()
     return fed.run_aggregation(lambda: _neighbors(fed, arrived, aggregator, t0))
 
@@ -635,11 +637,18 @@ def _neighbors(fed: Federation, arrived: Dict[str, Any], aggregator, t0: float) 
         return []
     learners = [fed.local_nodes[a].learner for a in local]
     if fed.mesh is not None and fed.mesh_size > 1:
-        _mesh_neighbors(fed, peers, index, w, local, learners)
+        _mesh_neighbors(fed, peers, index, w, local, learners, aggregator)
         fed.record("aggregate", time.perf_counter() - t0)
         return local
     group = _stacked_group(learners)
-    if fed.solo and group is not None and group.params.is_cuda and group.capacity <= 16 and group.S % 4 == 0:
+    clipped = getattr(aggregator, "clipped", False)  # ClippedGossip: the same plan of sources, clipped per neighbour
+    if clipped and fed.solo and group is not None and group.params.is_cuda and all(len(state_tensors(lr)) == 1 for lr in learners):
+        # the live rows of the stacked engine buffer, in place: three launches, no pack or unpack
+        src = {a: lr.flat_params() for a, lr in zip(local, learners)}
+        _publish_clipping(fed, aggregator, _clipped_mix(aggregator, peers, index, w, local, src))
+        fed.record("aggregate", time.perf_counter() - t0)
+        return local
+    if not clipped and fed.solo and group is not None and group.params.is_cuda and group.capacity <= 16 and group.S % 4 == 0:
         # every neighbour is a row of the same stacked engine buffer: the whole mixing step is one
         # in-place kernel (row p <- Σ_q M[p, q] row q); no per-peer pack / average / unpack launches
         mix = np.zeros((group.capacity, group.capacity), dtype=np.float32)
@@ -680,6 +689,13 @@ def _neighbors(fed: Federation, arrived: Dict[str, Any], aggregator, t0: float) 
         fed.batch_p2p_(ops_)
     src = dict(rows)
     src.update(recvs)
+    if clipped:
+        # the packed local rows are written in place; the received rows are sources only
+        _publish_clipping(fed, aggregator, _clipped_mix(aggregator, peers, index, w, local, src))
+        for a in local:
+            _unpack_into(fed.local_nodes[a].learner, rows[a])
+        fed.record("aggregate", time.perf_counter() - t0)
+        return local
     mixed = {}
     for a in local:
         i = index[a]
@@ -693,9 +709,10 @@ def _neighbors(fed: Federation, arrived: Dict[str, Any], aggregator, t0: float) 
     return local
 
 
-def _mesh_neighbors(fed: Federation, peers, index, w, local, learners) -> None:
+def _mesh_neighbors(fed: Federation, peers, index, w, local, learners, aggregator=None) -> None:
     """Topology mixing over a device mesh: every row a peer needs from another device arrives by
-    ONE grouped RCCL send/recv exchange (``rmesh_p2p``); the mix runs on the receiving device."""
+    ONE grouped RCCL send/recv exchange (``rmesh_p2p``); the mix runs on the receiving device
+    (a ``ClippedGossip``: one clipped mix per receiving device, the received rows as sources only)."""
     lr_of = dict(zip(local, learners))
     rank = {a: mesh_rank_of(lr_of[a]) for a in local}
     rows = {}
@@ -715,6 +732,16 @@ def _mesh_neighbors(fed: Federation, peers, index, w, local, learners) -> None:
     if ops_:
         fed.mesh.p2p_(ops_)
         fed.mesh_track("p2p")
+    if getattr(aggregator, "clipped", False):
+        for rd in sorted(set(rank.values())):
+            here = [a for a in local if rank[a] == rd]
+            src = {a: rows[a] for a in here}
+            src.update({b: t for (b, r), t in got.items() if r == rd})
+            with on_device(fed.devices[rd]):
+                _publish_clipping(fed, aggregator, _clipped_mix(aggregator, peers, index, w, here, src), here)
+                for a in here:
+                    _unpack_into(lr_of[a], rows[a])
+        return
     mixed = {}
     for a in local:
         i = index[a]
@@ -727,6 +754,40 @@ def _mesh_neighbors(fed: Federation, peers, index, w, local, learners) -> None:
     for a in local:
         with on_device(fed.devices[rank[a]]):
             _unpack_into(lr_of[a], mixed[a])
+
+
+def _clipped_mix(aggregator, peers, index, w, targets, src):
+    """One ``ops.clipped_gossip_into`` call over the rows of ``src`` (address -> flat fp32 row), in
+    peer order: the rows of ``targets`` are written in place, every other row is a source only (an
+    all-zero row of W). Row ``a``'s shares are ``w[a, b]`` over its present sources (itself
+    included), renormalised as the plain mix does, so an absent neighbour's share folds back
+    proportionally; the self share is implicit. Returns ``(addresses in row order, tau, w_eff)``."""
+    order = sorted(src, key=lambda a: index[a])
+    row = {a: r for r, a in enumerate(order)}
+    shares = np.zeros((len(order), len(order)), dtype=np.float64)
+    for a in targets:
+        i = index[a]
+        nz = [j for j in np.nonzero(w[i])[0] if peers[j] in src]
+        total = float(sum(w[i, j] for j in nz))
+        for j in nz:
+            if j != i:
+                shares[row[a], row[peers[j]]] = w[i, j] / total
+    with torch.no_grad():
+        _, tau, w_eff = ops.clipped_gossip_into([src[a] for a in order], shares, **aggregator.radius_args())
+    return order, tau, w_eff
+
+
+def _publish_clipping(fed: Federation, aggregator, clipping, addrs=None) -> None:
+    """``last_clipping = (addresses in row order, tau, w_eff)`` on the round's aggregator and on the
+    aggregators of the local peers among ``addrs`` (default: the rows). Device tensors: reading
+    them is the caller's synchronisation."""
+    written = [a for a in (clipping[0] if addrs is None else addrs) if a in fed.local_nodes]
+    for a in written:
+        fed.local_nodes[a].aggregator.last_clipping = clipping
+    # the round's aggregator is usually one peer's own: on a mesh it keeps the plan of that peer's device
+    owners = [a for a, node in fed.local_nodes.items() if node.aggregator is aggregator]
+    if not owners or set(owners) & set(written):
+        aggregator.last_clipping = clipping
 
 
 # aggregator kinds reduced on the device (no wire models, no host copies)

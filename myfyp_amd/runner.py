@@ -24,7 +24,7 @@ One description drives every experiment the examples, the CLI and the FYP harnes
         name: MLP               # MLP | LeNet5 | ResNet18, or package + model_build_fn
         params: {}              # + compression: {ptq: {dtype: float16}, topk: {k: 0.1}, zlib: {level: 6}}
       aggregator:
-        name: FedAvg            # FedAvg | FedMedian | Scaffold | FedProx | Krum | TrimmedMean | GeometricMedian | Bulyan
+        name: FedAvg            # FedAvg | FedMedian | Scaffold | FedProx | Krum | TrimmedMean | GeometricMedian | Bulyan | NeighborAvg | ClippedGossip
         params: {}
       attack: {node: 1, kind: sign_flip, sigma: 0.1, persistent: false}
       # or colluding attackers (collective protocol only): {kind: min_max, nodes: [1, 5], z: 1.0, eps: 0.5}
@@ -73,6 +73,7 @@ _AGGREGATORS = {
     "geomedian": ("myfyp_amd.learning.aggregators.geometric_median", "GeometricMedian"),
     "bulyan": ("myfyp_amd.learning.aggregators.bulyan", "Bulyan"),
     "neighboravg": ("myfyp_amd.learning.aggregators.neighbor_avg", "NeighborAvg"),
+    "clippedgossip": ("myfyp_amd.learning.aggregators.clipped_gossip", "ClippedGossip"),
 }
 _MODELS = {"mlp": "MLP", "lenet5": "LeNet5", "lenet": "LeNet5", "resnet18": "ResNet18", "resnet": "ResNet18"}
 
