@@ -280,6 +280,14 @@ __device__ __forceinline__ bf16x8 frag_b_tr_x(const bf16* base, int ld, int k0, 
   return __builtin_bit_cast(bf16x8, (mlp_s16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
 }
 
+// the same fragment from the address of its first read (C2's straight body: the lane's part of the
+// address is derived once per step, the K step, column half and batch tile added as constants)
+__device__ __forceinline__ bf16x8 frag_b_tr_at(const bf16* p0, int ld) {
+  const mlp_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((mlp_lds_s16x4*)(p0));
+  const mlp_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((mlp_lds_s16x4*)(p0 + 4 * ld));
+  return __builtin_bit_cast(bf16x8, (mlp_s16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+}
+
 // ---- LDS carving (16-byte aligned offsets)
 struct OwnerLds32 {
   int ldx;  // bf16 row stride of the X tile
@@ -356,7 +364,7 @@ __device__ __forceinline__ bool gang_commit(const MLPArgs& a, const MLPPersistF3
   return persist::wg_wait(pb.flags, FPP, p, FD, NR, pb.fbase + DONE_MARK, pb.err, sOk);
 }
 
-template <int BP, bool ADAM, bool EXTRA, int KS, bool RH, bool FUSE = false, int K24 = 0, int FRAG = 0>
+template <int BP, bool ADAM, bool EXTRA, int KS, bool RH, bool FUSE = false, int K24 = 0, int FRAG = 0, int D0C = 0>
 __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, int g, char* smem) {
   // FUSE: the forward of step t + 1 is accumulated inside C2 of step t, K step by K step, by the wave
   // that has just updated that K step's weights and staged its columns of the next batch
@@ -367,12 +375,23 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
   static_assert(FRAG == 0 || FUSE, "H1 fragment image: the fused layout-1 K-split-1 kernels only");
   constexpr int MT = BP / 16;
   constexpr int RQ = rq_of(KS);
+  // C2's straight body: every column of K step wave + 8q is known to lie below D0, so that the K
+  // step holds neither the bias column nor columns past it. A wave takes that body only with
+  // wave + 8 (RQ - 1) < KS1 = D0 / 32 + 1, i.e. 32 (wave + 8 (RQ - 1)) <= D0, which covers the K steps
+  // q < RQ - 1 whole; with D0 a constant, K step q's last wave (7) decides.
+  constexpr auto q_inside = [](int q) { return q < RQ - 1 || (D0C != 0 && q < RQ && 32 * (8 * q + 8) <= D0C); };
   constexpr int XPT = BP / 4;  // 16-byte X chunks per lane: 4 K steps x BP rows x 4 chunks / 64 lanes
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int h = lane >> 4, c = lane & 15;
   const int cg = g % NCG, kh = g / NCG;  // column group, K part
-  const int D0 = a.D0;
+  // D0C (MYFYP_F32_STATIC_D0): the input width as a constant of the instantiation (0: a.D0). With it
+  // KS1, LDX, the K steps per wave and the bias column's place are constants too: the X tile's row
+  // strides fold into the LDS instructions' immediates and no K step below the bias column's tests a
+  // column against D0. The launch takes such a kernel only where a.D0 == D0C.
+  static_assert(D0C == 0 || (FUSE && K24 == 1 && FRAG == 1 && D0C % 8 == 0 && D0C >= 768 && D0C / 32 + 1 <= KS1_MAX),
+                "static D0: the fused K24 fragment kernels, a width with a K step 24");
+  const int D0 = D0C != 0 ? D0C : a.D0;
   constexpr bool XR = xr_of(KS, RH);  // cross-XCD K split (see the constants above)
   const int s0 = kpart_begin(ks1_of(D0), KS, kh);  // first (global) K step of this owner; local K step j is global s0 + j
   const int KS1 = kpart_begin(ks1_of(D0), KS, kh + 1) - s0;  // local K steps of this owner (<= kh_of(D0, KS))
@@ -522,13 +541,18 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
   // are now and the batch tile currently staged in LDS. The LDS-resident K step (q == RQ, KS = 1:
   // K step 24, D0 > 767) is wave 0's. chk = false (C2's straight body): the caller knows the K step
   // exists, no test. rx (the K24 instantiations): the LDS-resident K step's weights are in w1x, not in sW1x.
-  auto fwd_kstep = [&](int q, f32x4(&acc)[MT], bool chk = true, bool rx = false) __attribute__((always_inline)) {
+  // xa (chk = false: C2's straight body, fused forward): the lane's A-fragment address of batch tile 0 in K step
+  // `wave`, derived by the caller once per step from the step's laundered lane; this K step's and the
+  // batch tiles' are constants away (256 q and 16 mt LDX elements).
+  auto fwd_kstep = [&](int q, f32x4(&acc)[MT], bool chk = true, bool rx = false, const bf16* xa = nullptr) __attribute__((always_inline)) {
     const int s = wave + 8 * q;
     if (chk && s >= KS1) return;
     // lane coordinates laundered per K step: the compiler would otherwise hoist every LDS address
-    // of the loop out of it and spill them
+    // of the loop out of it and spill them. Not in the straight body's calls (xa): they take no
+    // address from the lane here, and one base per step is what the step's own laundering allows
+    // (it lives inside one step, never across the step loop's back-edge, which is what was spilled).
     int lq = lane;
-    asm volatile("" : "+v"(lq));
+    if (chk) asm volatile("" : "+v"(lq));
     const int hq = lq >> 4, cq = lq & 15;
     float wq[8];
 #pragma unroll
@@ -542,6 +566,11 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
       bf16x8 af[MT];
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) {
+        if (!chk) {  // (not "xa != nullptr": a test the compiler keeps, and a branch per K step)
+          const bf16* xp = xa + 16 * mt * LDX + 256 * q;
+          af[mt] = cat8(*reinterpret_cast<const bf16x4*>(xp), *reinterpret_cast<const bf16x4*>(xp + 16));
+          continue;
+        }
         const bf16* xp = sX + (16 * mt + cq) * LDX + 32 * s + 4 * (hq & 1);
         af[mt] = cat8(*reinterpret_cast<const bf16x4*>(xp + ((hq >> 1) << 3)), *reinterpret_cast<const bf16x4*>(xp + ((2 + (hq >> 1)) << 3)));
       }
@@ -762,13 +791,29 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
     auto xq_load = [&](int q, bool chk = true) __attribute__((always_inline)) {
       const int s = wave + 8 * q;
       if (chk && s >= KS1) return;  // wave-uniform
-      // the straight body's calls take the step's laundered lane: their offsets differ by constants
-      // from K step to K step, where a lane laundered per call costs a 32-bit multiply per chunk
+      // the straight body's calls take the step's laundered lane: one offset per step (row (lx >> 2) of
+      // batch tile 0, chunk lx & 3 of K step `wave`), the same value in every call of the step, with
+      // the K step (512 q bytes, an immediate) and the batch tile (32 D0 kk bytes) added to it. The
+      // tile's term goes into the vector offset, not the scalar one: the rows past the batch rely on
+      // the range check, which is only known here to cover the vector offset and the immediate. Where every
+      // column of the K step is known to lie below D0 (q_inside) the offset is not tested against it.
+      if (!chk) {
+        const int lx = tv & 63;
+        const unsigned xb = (unsigned)((lx >> 2) * D0 + 8 * (lx & 3) + 32 * wave) * 2u;
+#pragma unroll
+        for (int kk = 0; kk < XQF; ++kk) {
+          unsigned off = xb + (unsigned)(kk * 16 * D0 + 256 * q) * 2u;
+          if (!q_inside(q)) {  // (laundered on both sides of the select: see below)
+            asm("" : "+v"(off));
+            off = 32 * s + 8 * (lx & 3) < D0 ? off : 0x7FFFFFF0u;
+            asm("" : "+v"(off));
+          }
+          xqf[kk] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r_xn, off, 0, 0));
+        }
+        return;
+      }
       int lx = lane;
-      if (chk)
-        asm volatile("" : "+v"(lx));
-      else
-        lx = tv & 63;
+      asm volatile("" : "+v"(lx));
 #pragma unroll
       for (int kk = 0; kk < XQF; ++kk) {
         const int idx = kk * 64 + lx;
@@ -784,7 +829,7 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
         xqf[kk] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r_xn, off, 0, 0));
       }
     };
-    if constexpr (FUSE) xq_load(0);
+    if constexpr (FUSE) xq_load(0, !ST);  // (the straight body: K step `wave` exists)
 
     // ================= C: backward of this slice
     const float* dh2_t = pb.dh2x + ((int64_t)p * 2 + (t & 1)) * BP * PD2 * 2;
@@ -911,6 +956,9 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
     // three-term split of dH1, W1 update, the next batch's columns staged right after this K
     // step's reads
     {
+      // the step's laundered lane: the guarded forms derive each chunk's addresses from it (and their
+      // LDS fragment addresses from a lane laundered per K step, lq below); the fused straight body
+      // derives one base per address family from it, once per step (xs_st / xs_tr / xs_fw, below)
       int lv = lane;
       asm volatile("" : "+v"(lv));
       f32x4 accF[FUSE ? MT : 1];  // fused loop: this wave's share of H1(t + 1)
@@ -952,6 +1000,27 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
           dfr[2][kb] = ld8(dfrag + 32 * LDT + 32 * kb);
         }
       }
+      // Fused forward, straight body: the lane's part of every X-tile address of the step, derived
+      // here once from the step's laundered lane lv, for K step `wave` and batch tile 0. The K steps
+      // (32 columns: 256 q elements on), the column halves, the chunks' rows and the batch tiles (16 or
+      // 32 rows of LDX elements) are wave-uniform terms on top: instruction immediates where LDX is a
+      // constant (D0C), scalar values else. Derived per K step and per chunk from a lane laundered
+      // there, this was 41 % of the straight block's vector instructions (profiles/r14_c2_addr/isa.md).
+      //   xs_st: the staging store of chunk lv & 3, row lv >> 2
+      //   xs_tr: frag_b_tr_x's first transposed read (column half 0, rows 0..31)
+      //   xs_fw: fwd_kstep's A fragment
+      //   b1_row: the lane's row if its chunk is the one at column D0 (in the K step that holds it),
+      //           else past every batch: the bias input is (b1_row < rows in K step D0 / 32) ? 1.0 : 0
+      const bf16 *xs_st = nullptr, *xs_tr = nullptr, *xs_fw = nullptr;
+      int b1_row = 0;
+      if (FUSE && ST) {
+        const int g4 = lv >> 4, c16 = lv & 15, pp = lv & 3;
+        const bf16* sXw = sX + 32 * wave;
+        xs_st = sXw + (lv >> 2) * LDX + 8 * pp;
+        xs_tr = sXw + (8 * g4 + (c16 >> 2)) * LDX + 8 * (pp >> 1) + 4 * (pp & 1);
+        xs_fw = sXw + c16 * LDX + 4 * (g4 & 1) + 8 * (g4 >> 1);
+        b1_row = 8 * pp == (D0 & 31) ? lv >> 2 : 0x7FFFFFFF;
+      }
 #pragma unroll
       for (int q = 0; q < QN; ++q) {
         if (q >= qn) continue;
@@ -961,8 +1030,10 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
         // LDS-resident K step, wave 0's
         const int s = wave + 8 * q;
         if (STq || s < KS1) {
+          // (the lane is laundered per K step for the guarded forms' addresses; the fused straight K
+          // steps take theirs from the step's bases above, and dH1's fragments from registers)
           int lq = lane;
-          asm volatile("" : "+v"(lq));
+          if (!(FUSE && STq)) asm volatile("" : "+v"(lq));
           const bf16* dfrag = sD3 + (lq & 15) * LDT + 8 * (lq >> 4);
           constexpr int XQ = BP / 16;
           // this lane's 16-byte chunks of the K step: chunk (lv & 3) of a row covers columns
@@ -993,7 +1064,7 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
 #pragma unroll
             for (int kb = 0; kb < BP / 32; ++kb) {
               if (FUSE && STq)  // the fragments read ahead of the loop
-                acc = mfma3(frag_b_tr_x(sX, LDX, 32 * kb, s, tt, lq), dfr[0][FUSE ? kb : 0], dfr[1][FUSE ? kb : 0], dfr[2][FUSE ? kb : 0], acc);
+                acc = mfma3(frag_b_tr_at(xs_tr + 32 * kb * LDX + 256 * q + 16 * tt, LDX), dfr[0][FUSE ? kb : 0], dfr[1][FUSE ? kb : 0], dfr[2][FUSE ? kb : 0], acc);
               else
                 acc = mfma3(frag_b_tr_x(sX, LDX, 32 * kb, s, tt, lq), ld8(dfrag + 32 * kb), ld8(dfrag + 16 * LDT + 32 * kb),
                             ld8(dfrag + 32 * LDT + 32 * kb), acc);
@@ -1033,7 +1104,15 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
             for (int kk = 0; kk < XQ; ++kk) {
               const int idx = kk * 64 + lv;
               const int r = idx >> 2, col = 32 * s + 8 * (idx & 3), gcol = C0 + col;
-              if (STq || (SI && q == RQ)) {  // branch-free: xq is zero at and past column D0 (D0 % 8 == 0)
+              if (FUSE && STq) {
+                // as below, from the step's base; the bias input only where the K step can hold column D0
+                unsigned x0 = xq[kk].x;
+                if (!q_inside(q)) {
+                  const int lim = 32 * s == (D0 & ~31) ? rows_next - 16 * kk : 0;  // wave-uniform
+                  x0 |= b1_row < lim ? 0x3F80u : 0u;
+                }
+                *reinterpret_cast<u32x4*>(const_cast<bf16*>(xs_st) + kk * 16 * LDX + 256 * q) = u32x4{x0, xq[kk].y, xq[kk].z, xq[kk].w};
+              } else if (STq || (SI && q == RQ)) {  // branch-free: xq is zero at and past column D0 (D0 % 8 == 0)
                 // (one 16-byte vector: the struct with one member rewritten was stored in 8-byte halves)
                 const unsigned b1 = (gcol == D0 && r < rows_next) ? 0x3F80u : 0u;  // bias input: bf16 1.0
                 *reinterpret_cast<u32x4*>(sX + r * LDX + col) = u32x4{xq[kk].x | b1, xq[kk].y, xq[kk].z, xq[kk].w};
@@ -1050,7 +1129,7 @@ __device__ void owner32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
         if constexpr (FUSE) {
           if (q + 1 < qn) xq_load(q + 1, !STq);
           if (STq)
-            fwd_kstep(q, accF, false, KR);
+            fwd_kstep(q, accF, false, KR, xs_fw);
           else if (more)
             fwd_kstep(q, accF);
         }
@@ -1984,7 +2063,7 @@ __device__ void headr32(const MLPArgs& a, const MLPPersistF32Bufs& pb, int p, in
 // flags offset by RETRY_BASE (the aborted attempt's flag values are all smaller), and on success
 // sets err[p] = 2 ("recovered"). Gangs are independent: one peer's give-up never aborts another.
 
-template <int BP, bool ADAM, bool EXTRA, int KS, bool RH = false, bool FUSE = false, int K24 = 0, int FRAG = 0>
+template <int BP, bool ADAM, bool EXTRA, int KS, bool RH = false, bool FUSE = false, int K24 = 0, int FRAG = 0, int D0C = 0>
 __global__ __launch_bounds__(NT) void mlp_persistent_f32_epoch(MLPArgs a, MLPPersistF32Bufs pb, int p_base, int attempt) {
   extern __shared__ __attribute__((aligned(16))) char smem_p32[];
   constexpr int PPL = ppl_of(KS, RH);
@@ -2052,7 +2131,7 @@ __global__ __launch_bounds__(NT) void mlp_persistent_f32_epoch(MLPArgs a, MLPPer
     if (role == 0 && threadIdx.x == 0 && p < 64) g_plain_seen[p] = pb.plain;
   }
   if (role < ng_of(KS))
-    owner32<BP, ADAM, EXTRA, KS, RH, FUSE, K24, FRAG>(a, pb, p, role, smem_p32);
+    owner32<BP, ADAM, EXTRA, KS, RH, FUSE, K24, FRAG, D0C>(a, pb, p, role, smem_p32);
   else if (RH)
     headr32<BP, ADAM, EXTRA, KS>(a, pb, p, role - ng_of(KS), smem_p32);
   else
@@ -2275,10 +2354,12 @@ bool v3_supported(const MLPArgs& a) {
   return persistent_f32_lds_ks(a, 1, true) <= 160 * 1024;
 }
 
-template <int BP, bool ADAM, bool EXTRA, int KS, bool RH = false, bool FUSE = false, int K24 = 0, int FRAG = 0>
+template <int BP, bool ADAM, bool EXTRA, int KS, bool RH = false, bool FUSE = false, int K24 = 0, int FRAG = 0, int D0C = 0>
 const void* f32_fn() {
-  return (const void*)mlp_persistent_f32_epoch<BP, ADAM, EXTRA, KS, RH, FUSE, K24, FRAG>;
+  return (const void*)mlp_persistent_f32_epoch<BP, ADAM, EXTRA, KS, RH, FUSE, K24, FRAG, D0C>;
 }
+// the input width the static-D0 kernels are built for (MNIST: 28 x 28)
+constexpr int STATIC_D0 = 784;
 // the fused forward (owner32's FUSE) is instantiated for layout 1 at K split 1 without an extra term
 __host__ __device__ constexpr bool fuse_inst(int KS, bool RH) { return KS == 1 && !RH; }
 template <int BP, int KS, bool RH = false>
@@ -2298,16 +2379,31 @@ hipError_t prepare_f32_bp(int lds) {
       const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
       if (e != hipSuccess) return e;
     }
+    // the MNIST width as a constant (owner32's D0C, MYFYP_F32_STATIC_D0): the K24 fragment kernels only
+    if constexpr (KS == 1) {
+      for (const void* fn : {f32_fn<BP, true, false, 1, RH, true, 1, 1, STATIC_D0>(), f32_fn<BP, false, false, 1, RH, true, 1, 1, STATIC_D0>()}) {
+        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (e != hipSuccess) return e;
+      }
+    }
   }
   return hipSuccess;
 }
 template <int BP, int KS, bool RH = false>
-void launch_f32_bp(const MLPArgs& a, const MLPPersistF32Bufs& pb, hipStream_t s, int p_base, size_t lds, int attempt, bool fuse, bool h1_frag) {
+void launch_f32_bp(const MLPArgs& a, const MLPPersistF32Bufs& pb, hipStream_t s, int p_base, size_t lds, int attempt, bool fuse, bool h1_frag,
+                   bool static_d0) {
   const dim3 grid(grid_of(KS, RH, RH ? roles3_of(KS, BP) : roles_of(KS))), block(NT);
   const bool adam = a.opt.kind == 0;
   const bool extra = a.anchor != nullptr || a.cg != nullptr;
   if constexpr (fuse_inst(KS, RH)) {
     if (fuse && !extra && h1_frag) {  // H1 and dH2 as fragment images (set by the launch where it applies)
+      if constexpr (KS == 1) {
+        if (pb.k24 == 1 && static_d0) {  // a.D0 == STATIC_D0 (set by the launch where it applies)
+          if (adam) hipLaunchKernelGGL((mlp_persistent_f32_epoch<BP, true, false, 1, RH, true, 1, 1, STATIC_D0>), grid, block, lds, s, a, pb, p_base, attempt);
+          else hipLaunchKernelGGL((mlp_persistent_f32_epoch<BP, false, false, 1, RH, true, 1, 1, STATIC_D0>), grid, block, lds, s, a, pb, p_base, attempt);
+          return;
+        }
+      }
       if (pb.k24 == 1) {
         if (adam) hipLaunchKernelGGL((mlp_persistent_f32_epoch<BP, true, false, KS, RH, true, 1, 1>), grid, block, lds, s, a, pb, p_base, attempt);
         else hipLaunchKernelGGL((mlp_persistent_f32_epoch<BP, false, false, KS, RH, true, 1, 1>), grid, block, lds, s, a, pb, p_base, attempt);
@@ -2572,6 +2668,26 @@ static int f32_h1_frag_mode() {
 extern "C" int mlp_set_f32_h1_frag(int mode) { return g_h1_frag_override.exchange(mode < 0 ? -1 : mode); }
 extern "C" int mlp_f32_h1_frag_last() { return g_h1_frag_last.load(std::memory_order_relaxed); }
 
+// MYFYP_F32_STATIC_D0: 1 (default) an epoch of input width 784 (MNIST) that takes the K24 fragment
+// kernels runs the instantiation with that width as a compile-time constant (owner32's D0C: strides
+// as immediates, no column tests below K step 24, no multiplies), 0 the run-time-width kernel (A/B;
+// same bits either way); mlp_set_f32_static_d0 overrides it (tests; -1: back to the environment).
+// Values above 1 are taken as 1. Every other width takes the run-time kernel whatever the switch
+// says. mlp_f32_static_d0_last: what the last epoch launch took (-1: none yet).
+static std::atomic<int> g_static_d0_override{-1};
+static std::atomic<int> g_static_d0_last{-1};
+static int f32_static_d0_mode() {
+  const int o = g_static_d0_override.load(std::memory_order_relaxed);
+  if (o >= 0) return o;
+  static const int v = [] {
+    const char* e = getenv("MYFYP_F32_STATIC_D0");
+    return e != nullptr ? atoi(e) : 1;
+  }();
+  return v;
+}
+extern "C" int mlp_set_f32_static_d0(int mode) { return g_static_d0_override.exchange(mode < 0 ? -1 : mode); }
+extern "C" int mlp_f32_static_d0_last() { return g_static_d0_last.load(std::memory_order_relaxed); }
+
 hipError_t mlp_launch_persistent_f32_epoch(const MLPArgs& a, const MLPPersistF32Bufs& pb_in, hipStream_t s, bool zero_flags, const int* active) {
   MLPPersistF32Bufs pb = pb_in;
   pb.plain_ok = mlp_plain_pub_mode();
@@ -2584,6 +2700,7 @@ hipError_t mlp_launch_persistent_f32_epoch(const MLPArgs& a, const MLPPersistF32
   }
   if (f32_variant(a) == 2) {
     g_h1_frag_last.store(0, std::memory_order_relaxed);
+    g_static_d0_last.store(0, std::memory_order_relaxed);
     mlp_f32v2_launch(a, pb, s);
     return hipGetLastError();
   }
@@ -2600,6 +2717,8 @@ hipError_t mlp_launch_persistent_f32_epoch(const MLPArgs& a, const MLPPersistF32
   g_k24_last.store(pb.k24, std::memory_order_relaxed);
   const bool h1_frag = f32_h1_frag_mode() > 0 && fuse && pb.dh2_frag == 1;
   g_h1_frag_last.store(h1_frag ? 1 : 0, std::memory_order_relaxed);
+  const bool static_d0 = f32_static_d0_mode() > 0 && h1_frag && pb.k24 == 1 && KS == 1 && !rh && a.D0 == STATIC_D0;
+  g_static_d0_last.store(static_d0 ? 1 : 0, std::memory_order_relaxed);
   // groups of ppl peers: one launch each (a launch's gangs must all be co-resident), then the
   // recovery launches (attempt 1): a no-op exit for every gang that did not give up
   // (a group with no active peer is not launched: at one peer per device and K split 8 the other
@@ -2616,22 +2735,22 @@ hipError_t mlp_launch_persistent_f32_epoch(const MLPArgs& a, const MLPPersistF32
       if (!group_live(p0)) continue;
       if (rh) {
         if (KS == 2) {
-          if (a.Bpad == 64) launch_f32_bp<64, 2, true>(a, pb, s, p0, lds, attempt, fuse, h1_frag);
-          else launch_f32_bp<32, 2, true>(a, pb, s, p0, lds, attempt, fuse, h1_frag);
+          if (a.Bpad == 64) launch_f32_bp<64, 2, true>(a, pb, s, p0, lds, attempt, fuse, h1_frag, static_d0);
+          else launch_f32_bp<32, 2, true>(a, pb, s, p0, lds, attempt, fuse, h1_frag, static_d0);
         } else {
-          if (a.Bpad == 64) launch_f32_bp<64, 1, true>(a, pb, s, p0, lds, attempt, fuse, h1_frag);
-          else launch_f32_bp<32, 1, true>(a, pb, s, p0, lds, attempt, fuse, h1_frag);
+          if (a.Bpad == 64) launch_f32_bp<64, 1, true>(a, pb, s, p0, lds, attempt, fuse, h1_frag, static_d0);
+          else launch_f32_bp<32, 1, true>(a, pb, s, p0, lds, attempt, fuse, h1_frag, static_d0);
         }
       } else if (KS == 8) {
-        launch_f32_bp<64, 8>(a, pb, s, p0, lds, attempt, fuse, h1_frag);  // (f32_ks_wanted: Bpad 64 only)
+        launch_f32_bp<64, 8>(a, pb, s, p0, lds, attempt, fuse, h1_frag, static_d0);  // (f32_ks_wanted: Bpad 64 only)
       } else if (KS == 4) {
-        launch_f32_bp<64, 4>(a, pb, s, p0, lds, attempt, fuse, h1_frag);
+        launch_f32_bp<64, 4>(a, pb, s, p0, lds, attempt, fuse, h1_frag, static_d0);
       } else if (KS == 2) {
-        if (a.Bpad == 64) launch_f32_bp<64, 2>(a, pb, s, p0, lds, attempt, fuse, h1_frag);
-        else launch_f32_bp<32, 2>(a, pb, s, p0, lds, attempt, fuse, h1_frag);
+        if (a.Bpad == 64) launch_f32_bp<64, 2>(a, pb, s, p0, lds, attempt, fuse, h1_frag, static_d0);
+        else launch_f32_bp<32, 2>(a, pb, s, p0, lds, attempt, fuse, h1_frag, static_d0);
       } else {
-        if (a.Bpad == 64) launch_f32_bp<64, 1>(a, pb, s, p0, lds, attempt, fuse, h1_frag);
-        else launch_f32_bp<32, 1>(a, pb, s, p0, lds, attempt, fuse, h1_frag);
+        if (a.Bpad == 64) launch_f32_bp<64, 1>(a, pb, s, p0, lds, attempt, fuse, h1_frag, static_d0);
+        else launch_f32_bp<32, 1>(a, pb, s, p0, lds, attempt, fuse, h1_frag, static_d0);
       }
     }
   return hipGetLastError();

@@ -123,6 +123,8 @@ _SIGNATURES = {
     "mlp_f32_dh2_frag_last": (c_int, []),  # 1: the last fp32 epoch launch took it (0: layouts 2 / 3 or switched off)
     "mlp_set_f32_h1_frag": (c_int, [c_int]),  # H1 handed over in MFMA fragment order, H2 / dH2 transposed: 1 / 0 (-1: MYFYP_F32_H1_FRAG)
     "mlp_f32_h1_frag_last": (c_int, []),  # 1: the last fp32 epoch launch took it (fused layout-1 K-split-1 kernels, dH2 fragments on)
+    "mlp_set_f32_static_d0": (c_int, [c_int]),  # input width 784 as a compile-time constant of the epoch kernel: 1 / 0 (-1: MYFYP_F32_STATIC_D0)
+    "mlp_f32_static_d0_last": (c_int, []),  # 1: the last fp32 epoch launch took the static-width kernel (D0 = 784, K24 fragment kernels)
     # direct drive of the step-path kernels on a caller-built MLPArgs (tests/test_mlp_fused_gpu.py)
     "mlp_debug_args_size": (c_int, []),
     "mlp_debug_args_abi": (c_int, [c_void_p]),

@@ -92,6 +92,9 @@ h1_frag_last = getattr(lib, "mlp_f32_h1_frag_last", None)
 if h1_frag_last is not None:
     # (fragment image: the heads' "H1 load" ends when the loads are issued, their latency is in "H2+PL")
     print("H1 hand-off:", "fragment image, H2 and dH2 transposed (MYFYP_F32_H1_FRAG=1)" if h1_frag_last() == 1 else "[b][256] image staged through LDS")
+static_d0_last = getattr(lib, "mlp_f32_static_d0_last", None)
+if static_d0_last is not None:
+    print("input width:", "compile-time constant 784 (MYFYP_F32_STATIC_D0=1)" if static_d0_last() == 1 else "run-time value")
 print("owner H1 published -> head H1 seen (us; fused: negative while the head is still in step t - 1):", [round((st[1, t, 1] - st[0, t, 2]) / 100.0, 2) for t in range(2, 10)])
 print("head dH2 published -> owner dH2 seen (us):", [round((st[0, t, 4] - st[1, t, 7]) / 100.0, 2) for t in range(2, 10)])
 print("head PL published -> head PL all seen (us):", [round((st[1, t, 5] - st[1, t, 4]) / 100.0, 2) for t in range(2, 10)])
