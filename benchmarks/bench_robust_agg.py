@@ -1,9 +1,10 @@
-"""Krum / TrimmedMean / GeometricMedian / Bulyan aggregation on the collective plane: device path against the generic path.
+"""Krum / TrimmedMean / GeometricMedian / Bulyan / DnC aggregation on the collective plane: device path against the generic path.
 
     python benchmarks/bench_robust_agg.py                      # MLP (n = 235,146) and ResNet-18, 8 peers
     python benchmarks/bench_robust_agg.py --models mlp --repeats 30
     python benchmarks/bench_robust_agg.py --aggregators geometric_median,krum
     python benchmarks/bench_robust_agg.py --aggregators bulyan
+    python benchmarks/bench_robust_agg.py --aggregators dnc,krum   # DnC's sqdist/select pair beside Krum's, all tiles and subsample_dims = 10000
     python benchmarks/bench_robust_agg.py --attack               # ops.collude_into (ALIE, IPM, min-max, min-sum) beside Krum, K = 8 / 16
 
 For each model and aggregator the same 8 co-located peers are aggregated two ways, alternating in
@@ -23,7 +24,9 @@ difference of a 5-step and a 1-step call, divided by 4: allocation and call over
 whole 1-step call (screen + one step: two pairs) is reported next to Krum's distance/select pair,
 which is timed in the same process for that. Bulyan's ``k_bulyan_mean<K, f>`` is timed alone from a
 selection made before the window, next to ``k_trimmed_mean<K>`` on the same rows in the same
-process. One JSON line per (model, aggregator). Needs a GPU:
+process. DnC's ``k_dnc_sqdist<K>`` / ``k_dnc_select`` pair is timed with every tile taken and at
+``subsample_dims = 10000`` (it then reads about 10000 / n of the bytes), next to Krum's pair in the
+same process. One JSON line per (model, aggregator). Needs a GPU:
 ``--device cpu`` only rehearses the plumbing and its timings mean nothing.
 """
 
@@ -106,12 +109,13 @@ def run_case(model_name: str, agg_name: str, args) -> dict:
     import torch
 
     from myfyp_amd import ops
-    from myfyp_amd.learning.aggregators import Bulyan, GeometricMedian, Krum, TrimmedMean
+    from myfyp_amd.learning.aggregators import Bulyan, DnC, GeometricMedian, Krum, TrimmedMean
     from myfyp_amd.parallel import weights_plane
     from myfyp_amd.parallel.federation import Federation
 
     make = {"krum": lambda: Krum(num_byzantine=1, multi=3), "trimmed_mean": lambda: TrimmedMean(beta=0.125),
-            "geometric_median": lambda: GeometricMedian(iters=3), "bulyan": lambda: Bulyan(num_byzantine=1)}[agg_name]
+            "geometric_median": lambda: GeometricMedian(iters=3), "bulyan": lambda: Bulyan(num_byzantine=1),
+            "dnc": lambda: DnC(num_byzantine=1)}[agg_name]
     Federation.reset()
     fed = Federation.init()
     nodes = build_nodes(model_name, make)
@@ -127,7 +131,8 @@ def run_case(model_name: str, agg_name: str, args) -> dict:
         rows0 = torch.stack([(-base if i == FLIPPED else base + 1e-3 * (1 + 0.15 * i) * 0.05 * torch.randn(n, generator=g)) for i in range(PEERS)]).to(dev)
         agg = nodes[0].aggregator
         device_fn = {"krum": weights_plane.aggregate_krum, "trimmed_mean": weights_plane.aggregate_trimmed_mean,
-                     "geometric_median": weights_plane.aggregate_geometric_median, "bulyan": weights_plane.aggregate_bulyan}[agg_name]
+                     "geometric_median": weights_plane.aggregate_geometric_median, "bulyan": weights_plane.aggregate_bulyan,
+                     "dnc": lambda f_, arrived, a: weights_plane.aggregate_dnc(f_, arrived, a, 0)}[agg_name]
 
         def restore() -> None:
             with torch.no_grad():
@@ -216,6 +221,21 @@ def run_case(model_name: str, agg_name: str, args) -> dict:
             kernels["trimmed_mean (same rows, same process)"] = {"ms": round(ms_trim, 4), "GBps": round(2 * PEERS * n * 4 / ms_trim / 1e6, 1),
                                                                  "bytes": "K rows read, P rows written"}
             kernels["whole call (3 launches)"] = {"ms": round(ms_all, 4)}
+        elif agg_name == "dnc":
+            scratch = [torch.empty(n, dtype=torch.float32, device=dev) for _ in range(PEERS)]
+            ms_all_tiles = event_ms(dev, lambda: ops.dnc_into(flats, [], w, 1, subsample_dims=None), it, wu)
+            ms_sub = event_ms(dev, lambda: ops.dnc_into(flats, [], w, 1, subsample_dims=10000), it, wu)
+            ms_sub3 = event_ms(dev, lambda: ops.dnc_into(flats, [], w, 1, iters=3, subsample_dims=10000), it, wu)
+            ms_krum = event_ms(dev, lambda: ops.krum_into(flats, [], w, 1, 3), it, wu)
+            ms_whole = event_ms(dev, lambda: ops.dnc_into(flats, scratch, w, 1, subsample_dims=10000), it, wu)
+            taken = float(ops.dnc_tiles(n, 0, 0, 1, 10000)[3].mean())
+            kernels["dnc_sqdist+select (all tiles)"] = {"ms": round(ms_all_tiles, 4), "GBps": round(PEERS * n * 4 / ms_all_tiles / 1e6, 1), "bytes": "K rows read"}
+            kernels["dnc_sqdist+select (subsample_dims 10000)"] = {"ms": round(ms_sub, 4), "tiles_taken": round(taken, 4),
+                                                                   "GBps": round(taken * PEERS * n * 4 / ms_sub / 1e6, 1), "bytes": "the taken tiles of K rows read"}
+            kernels["dnc_sqdist+select (subsample_dims 10000, iters 3)"] = {"ms": round(ms_sub3, 4)}
+            kernels["krum pairwise_sqdist+select (same rows, same process)"] = {"ms": round(ms_krum, 4), "GBps": round(PEERS * n * 4 / ms_krum / 1e6, 1),
+                                                                               "bytes": "K rows read"}
+            kernels["whole call (3 launches, subsample_dims 10000)"] = {"ms": round(ms_whole, 4)}
         else:
             scratch = [torch.empty(n, dtype=torch.float32, device=dev) for _ in range(PEERS)]
             ms = event_ms(dev, lambda: ops.trimmed_mean_into(flats, scratch, 1), it, wu)

@@ -79,6 +79,30 @@ void fl_bulyan(float* work, const OutPtrs& outs, int P, const RowPtrs& rows, int
                float* coef, hipStream_t s);
 // The last of fl_bulyan's launches alone: coef[K] in device memory marks the K - 2f picked rows.
 void fl_bulyan_mean(const OutPtrs& outs, int P, const RowPtrs& rows, int K, int f, const float* coef, int64_t n, hipStream_t s);
+// Divide-and-Conquer (DnC; Shejwalkar & Houmansadr, NDSS 2021) of rows 0..K-1: per iteration t <
+// iters (1..DNC_MAX_ITERS) the distances of fl_krum_select over a subsample of the coordinates, on
+// the same grid (work holds iters * fl_krum_grid(n, K) * K(K-1)/2 floats); the rows of non-finite
+// distances screened; the centred Gram matrix G = -1/2 J D J of the others, its top eigenpair
+// (lam, u) by repeated squaring, the scores lam * u_i^2 (+inf for a screened row) and the m highest
+// removed (the higher row first among equals; screened rows always go, and count towards m). A row
+// is kept iff every iteration keeps it; out rows 0..P-1 <- sum_k coef[k] * row k with coef[k] =
+// w_k / sum of the kept w, 0 for the others (nothing kept: every row, coef[k] = w_k / sum of w).
+// Outputs may alias rows; P == 0: selection only. Coordinates go in tiles of 256 (coordinates
+// 256 tau .. 256 tau + 255): with all == 0, tile tau of iteration t is taken iff
+// splitmix64(key[t] ^ tau) < thr or tau == forced[t]; with all != 0 every tile is, and the slabs
+// equal fl_krum_select's bit for bit. Device outputs dist[iters*K*K], score[iters*K], lam[iters]
+// (double), removed[K] (int: the first iteration that removed the row, or -1) and coef[K] (float).
+// Three launches: k_dnc_sqdist (gridDim.y = iters), k_dnc_select, k_coef_mean when P > 0. K == 1
+// issues only the mean: no pair exists, and the caller has stored coef[0] (and the other outputs).
+#define DNC_MAX_ITERS 8
+struct DncTiles {
+  uint64_t key[DNC_MAX_ITERS];
+  uint64_t forced[DNC_MAX_ITERS];
+  uint64_t thr;
+  int all;
+};
+void fl_dnc(float* work, const OutPtrs& outs, int P, const RowPtrs& rows, const RowW& w, int K, int m, int iters, const DncTiles& tiles, int64_t n,
+            double* dist, double* score, double* lam, int* removed, float* coef, hipStream_t s);
 // ClippedGossip (He, Karimireddy, Jaggi, 2022) of rows 0..K-1 in place: row p moves towards each
 // neighbour q (w[p][q] > 0, q != p; the diagonal is ignored) by at most a radius,
 //   x_p <- x_p + sum_q w_eff[p][q] (x_q - x_p),  w_eff[p][q] = float(w[p][q] * min(1, tau_p / |x_q - x_p|)).

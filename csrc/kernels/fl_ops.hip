@@ -1277,6 +1277,245 @@ __global__ __launch_bounds__(FL_BLOCK) void k_scale_add_noise(float* __restrict_
   }
 }
 
+// Divide-and-Conquer (DnC; Shejwalkar & Houmansadr, NDSS 2021) in three launches:
+//   k_dnc_sqdist<K>: k_pairwise_sqdist<K> over a subsample of the coordinates, one slab block of
+//                    work[iters][grid][K(K-1)/2] per iteration (gridDim.y = iters)
+//   k_dnc_select   : one block; per iteration the slabs summed as k_krum_select does, the rows of
+//                    non-finite distances screened, the centred Gram matrix G = −½·J·D·J of the rest
+//                    (J = I − 11ᵀ/K_v), its top eigenpair by repeated squaring, the scores λ·u_i² and
+//                    the m highest removed; then the iterations intersected: dist / score / lam /
+//                    removed / coef
+//   k_coef_mean<K> : out rows <- Σ_k coef[k] · row_k
+// The coordinates are subsampled in tiles of 256: the 64 float4 groups one wave loads at a time,
+// so the test is wave-uniform and no cache line is half used. Tile τ of iteration t is taken iff
+// splitmix64(key[t] ^ τ) < thr or τ == forced[t] (the host derives key, thr and forced from the
+// seed and the round); all != 0 takes every tile and hashes nothing.
+
+// Same body and accumulation order as k_pairwise_sqdist<K, VEC>: with every tile taken, block b of
+// iteration t stores the slab k_pairwise_sqdist's block b stores, bit for bit. g >> 6 is the same
+// in all lanes of a wave (FL_BLOCK and the grid stride are multiples of 64): it goes through
+// readfirstlane, so the hash is scalar work and the skip a scalar branch. Every register index is
+// static.
+template <int K, bool VEC>
+__global__ __launch_bounds__(FL_BLOCK) void k_dnc_sqdist(float* __restrict__ work, RowPtrs rows, DncTiles tiles, int64_t n) {
+  constexpr int NP = K * (K - 1) / 2;
+  __shared__ float part[KRUM_WAVES][NP];
+  float acc[NP];
+#pragma unroll
+  for (int q = 0; q < NP; ++q) acc[q] = 0.f;
+  const int it = blockIdx.y;
+  const uint64_t key = tiles.key[it], forced = tiles.forced[it];
+  const int64_t groups = (n + 3) / 4;
+  const int64_t stride = (int64_t)gridDim.x * FL_BLOCK;
+  for (int64_t g = (int64_t)blockIdx.x * FL_BLOCK + threadIdx.x; g < groups; g += stride) {
+    if (!tiles.all) {
+      const int64_t tg = g >> 6;
+      const uint64_t tau = ((uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(tg >> 32)) << 32) |
+                           (uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(tg & 0xFFFFFFFFll));
+      if (!(splitmix64(key ^ tau) < tiles.thr || tau == forced)) continue;
+    }
+    float4 v[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = load4<VEC>(rows.p[k], g, n);
+    int q = 0;
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+#pragma unroll
+      for (int j = i + 1; j < K; ++j) {
+        const float dx = v[i].x - v[j].x, dy = v[i].y - v[j].y, dz = v[i].z - v[j].z, dw = v[i].w - v[j].w;
+        acc[q] += (dx * dx + dy * dy) + (dz * dz + dw * dw);
+        ++q;
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < NP; ++q) {
+    float s = acc[q];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+    acc[q] = s;
+  }
+  const int wave = threadIdx.x / 64;
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int q = 0; q < NP; ++q) part[wave][q] = acc[q];
+  }
+  __syncthreads();
+  if (threadIdx.x < NP) {
+    float s = part[0][threadIdx.x];
+#pragma unroll
+    for (int w = 1; w < KRUM_WAVES; ++w) s += part[w][threadIdx.x];
+    work[((int64_t)it * gridDim.x + blockIdx.x) * NP + threadIdx.x] = s;
+  }
+}
+
+// One block. Per iteration it (slabs work[it][G][K(K-1)/2], summed by krum_sum_slabs into D):
+//  1 screen : row i is screened when more than half of its K−1 distances are non-finite; then, j
+//             ascending, an unscreened row j with a non-finite distance to an unscreened row i < j
+//             is screened too. V: the unscreened rows, K_v of them. Screened rows score +inf.
+//  2 centre : r_i = (Σ_{j∈V} D_ij) / K_v and c = (Σ_{i∈V} r_i) / K_v, both sums ascending;
+//             A_ij = −½ (((D_ij − r_i) − r_j) + c), G_ij = ½ (A_ij + A_ji); rows outside V hold 0.
+//             K_v <= 1 or tr G <= 0: λ = 0 and every score on V is 0.
+//  3 eigen  : M <- G / tr G; 20 times M <- M·M (thread (i, j) of the first 256 sums M_ik·M_kj over k
+//             ascending, one fma per term) and M <- M / tr M; j* = argmax_j M_jj (the lowest on a
+//             tie), u = M[:, j*] / |M[:, j*]|, λ = uᵀ(G u), s_i = λ·u_i². All in double, in LDS.
+//  4 remove : the m highest scores, the higher row first among equals; screened rows always go.
+// Then removed[k] = the first iteration that removed row k (−1: kept in all of them) and
+// coef[k] = float(w_k / Σ_kept w) for a kept row, else 0; nothing kept (screening only): w_k / Σ w
+// over all rows. Sums of weights 0: the plain mean of those rows, as k_krum_select.
+#define DNC_SQUARINGS 20
+__global__ __launch_bounds__(KRUM_SELECT_BLOCK) void k_dnc_select(const float* __restrict__ work, int G, int K, int m, int iters, RowW w,
+                                                                  double* __restrict__ dist, double* __restrict__ score, double* __restrict__ lam,
+                                                                  int* __restrict__ removed, float* __restrict__ coef) {
+  __shared__ double d[16][16];
+  __shared__ double gm[16][16];
+  __shared__ double ma[16][16];
+  __shared__ double mb[16][16];
+  __shared__ double part[KRUM_SELECT_BLOCK];
+  __shared__ double rmean[16], u[16], gu[16], sc[16];
+  __shared__ double cen, trg;
+  __shared__ unsigned screened;
+  __shared__ int jstar;
+  __shared__ int rem[16];
+  const int t = threadIdx.x;
+  const int i = (t >> 4) & 15, j = t & 15;  // the matrix entry of thread t < 256
+  const int NP = K * (K - 1) / 2;
+  const double inf = __builtin_huge_val();
+  if (t < 16) rem[t] = -1;
+  for (int it = 0; it < iters; ++it) {
+    krum_sum_slabs(work + (int64_t)it * G * NP, G, K, d, part);  // ends with a barrier
+    for (int q = t; q < K * K; q += KRUM_SELECT_BLOCK) dist[(int64_t)it * K * K + q] = d[q / K][q % K];
+    if (t == 0) {
+      unsigned s = 0;
+      for (int a = 0; a < K; ++a) {
+        int bad = 0;
+        for (int b = 0; b < K; ++b)
+          if (b != a && !__builtin_isfinite(d[a][b])) ++bad;
+        if (2 * bad > K - 1) s |= 1u << a;
+      }
+      for (int b = 1; b < K; ++b) {
+        if ((s >> b) & 1u) continue;
+        for (int a = 0; a < b; ++a)
+          if (!((s >> a) & 1u) && !__builtin_isfinite(d[a][b])) {
+            s |= 1u << b;
+            break;
+          }
+      }
+      screened = s;
+    }
+    __syncthreads();
+    const unsigned S = screened;
+    const int kv = K - __popc(S);
+    const bool vi = i < K && !((S >> i) & 1u), vj = j < K && !((S >> j) & 1u);
+    if (t < 16) {
+      double s = 0.0;
+      if (t < K && !((S >> t) & 1u)) {
+        for (int b = 0; b < K; ++b)
+          if (!((S >> b) & 1u)) s += d[t][b];
+        s /= (double)kv;
+      }
+      rmean[t] = s;
+    }
+    __syncthreads();
+    if (t == 0) {
+      double s = 0.0;
+      for (int a = 0; a < K; ++a)
+        if (!((S >> a) & 1u)) s += rmean[a];
+      cen = kv > 0 ? s / (double)kv : 0.0;
+    }
+    __syncthreads();
+    if (t < 256) ma[i][j] = (vi && vj) ? -0.5 * (((d[i][j] - rmean[i]) - rmean[j]) + cen) : 0.0;
+    __syncthreads();
+    if (t < 256) gm[i][j] = 0.5 * (ma[i][j] + ma[j][i]);
+    __syncthreads();
+    if (t == 0) {
+      double s = 0.0;
+      for (int a = 0; a < 16; ++a) s += gm[a][a];
+      trg = s;
+    }
+    __syncthreads();
+    const double tr0 = trg;
+    const bool flat = kv <= 1 || !(tr0 > 0.0);  // one barrier-uniform decision: trg is shared
+    if (!flat) {
+      if (t < 256) ma[i][j] = gm[i][j] / tr0;
+      __syncthreads();
+      for (int r = 0; r < DNC_SQUARINGS; ++r) {
+        if (t < 256) {
+          double s = 0.0;
+#pragma unroll
+          for (int k = 0; k < 16; ++k) s = fma(ma[i][k], ma[k][j], s);
+          mb[i][j] = s;
+        }
+        __syncthreads();
+        if (t < 256) {
+          double tr = 0.0;
+#pragma unroll
+          for (int k = 0; k < 16; ++k) tr += mb[k][k];
+          ma[i][j] = mb[i][j] / tr;
+        }
+        __syncthreads();
+      }
+      if (t == 0) {
+        int best = 0;
+        for (int a = 1; a < 16; ++a)
+          if (ma[a][a] > ma[best][best]) best = a;
+        jstar = best;
+      }
+      __syncthreads();
+      if (t < 16) {
+        const int js = jstar;
+        double nn = 0.0;
+        for (int a = 0; a < 16; ++a) nn = fma(ma[a][js], ma[a][js], nn);
+        u[t] = ma[t][js] / sqrt(nn);
+      }
+      __syncthreads();
+      if (t < 16) {
+        double s = 0.0;
+        for (int b = 0; b < 16; ++b) s = fma(gm[t][b], u[b], s);
+        gu[t] = s;
+      }
+      __syncthreads();
+    }
+    if (t < K) {
+      double l = 0.0;
+      if (!flat)
+        for (int a = 0; a < 16; ++a) l = fma(u[a], gu[a], l);
+      const double s = ((S >> t) & 1u) ? inf : (flat ? 0.0 : l * (u[t] * u[t]));
+      sc[t] = s;
+      score[it * K + t] = s;
+      if (t == 0) lam[it] = l;
+    }
+    __syncthreads();
+    if (t < K) {
+      int rank = 0;  // rows removed before row t
+      for (int b = 0; b < K; ++b)
+        if (b != t && (sc[b] > sc[t] || (sc[b] == sc[t] && b > t))) ++rank;
+      if ((((S >> t) & 1u) || rank < m) && rem[t] < 0) rem[t] = it;
+    }
+    __syncthreads();
+  }
+  if (t < K) {
+    double ws = 0.0, wall = 0.0;
+    int cnt = 0;
+    float wt = 0.f;
+    for (int b = 0; b < K; ++b) {
+      const float wb = w.w[b];
+      if (b == t) wt = wb;
+      wall += (double)wb;
+      if (rem[b] < 0) {
+        ws += (double)wb;
+        ++cnt;
+      }
+    }
+    removed[t] = rem[t];
+    float c;
+    if (cnt == 0) c = wall > 0.0 ? (float)((double)wt / wall) : 1.f / (float)K;
+    else if (rem[t] >= 0) c = 0.f;
+    else c = ws > 0.0 ? (float)((double)wt / ws) : 1.f / (float)cnt;
+    coef[t] = c;
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 void fl_weighted_sum(float* out, const uint64_t* srcs, const float* w, int K, int64_t n, bool srcs_aligned16, hipStream_t s) {
   const dim3 g(grid_for(n / 4 + 1)), b(FL_BLOCK);
@@ -1413,6 +1652,28 @@ void fl_bulyan(float* work, const OutPtrs& outs, int P, const RowPtrs& rows, int
   hipLaunchKernelGGL(k_bulyan_select, dim3(1), dim3(KRUM_SELECT_BLOCK), 0, s, work, (int)grid, K, f, dist, score, pick, coef);
   if (P > 0) fl_bulyan_mean(outs, P, rows, K, f, coef, n, s);
 }
+void fl_dnc(float* work, const OutPtrs& outs, int P, const RowPtrs& rows, const RowW& w, int K, int m, int iters, const DncTiles& tiles, int64_t n,
+            double* dist, double* score, double* lam, int* removed, float* coef, hipStream_t s) {
+  if (K < 1 || K > 16 || iters < 1 || iters > DNC_MAX_ITERS) return;
+  if (K > 1) {
+    const unsigned grid = fl_krum_grid(n, K);
+    const bool vec = all_aligned16(rows, K, nullptr, 0);
+    const dim3 g(grid, iters), b(FL_BLOCK);
+    switch (K) {
+#define DNC_CASE(KK)                                                                            \
+  case KK:                                                                                      \
+    if (vec) hipLaunchKernelGGL((k_dnc_sqdist<KK, true>), g, b, 0, s, work, rows, tiles, n);    \
+    else hipLaunchKernelGGL((k_dnc_sqdist<KK, false>), g, b, 0, s, work, rows, tiles, n);       \
+    break;
+      DNC_CASE(2) DNC_CASE(3) DNC_CASE(4) DNC_CASE(5) DNC_CASE(6) DNC_CASE(7) DNC_CASE(8)
+      DNC_CASE(9) DNC_CASE(10) DNC_CASE(11) DNC_CASE(12) DNC_CASE(13) DNC_CASE(14) DNC_CASE(15) DNC_CASE(16)
+#undef DNC_CASE
+      default: return;
+    }
+    hipLaunchKernelGGL(k_dnc_select, dim3(1), dim3(KRUM_SELECT_BLOCK), 0, s, work, (int)grid, K, m, iters, w, dist, score, lam, removed, coef);
+  }
+  if (P > 0) fl_coef_mean(outs, P, rows, K, coef, n, s);
+}
 void fl_geometric_median(float* work, const RowPtrs& rows, const RowW& w, int K, int iters, double nu, int64_t n, float* coef, double* dist,
                          double* obj, hipStream_t s) {
   const unsigned grid = fl_krum_grid(n, K);
@@ -1499,7 +1760,7 @@ void fl_scale_add_noise(float* t, int64_t n, float scale, float sigma, uint64_t 
 extern "C" int myfyp_warm_fl_ops() {
   hipFuncAttributes attr;
   // the robust aggregators' launches of the headline peer count (8) resolve here too, so a first
-  // Krum / trimmed-mean / geometric-median / Bulyan round pays no lookup behind a running epoch
+  // Krum / trimmed-mean / geometric-median / Bulyan / DnC round pays no lookup behind a running epoch
   const void* fns[] = {reinterpret_cast<const void*>(&k_weighted_sum<true>),
                        reinterpret_cast<const void*>(&k_trimmed_mean<8>),
                        reinterpret_cast<const void*>(&k_pairwise_sqdist<8, true>),
@@ -1508,7 +1769,9 @@ extern "C" int myfyp_warm_fl_ops() {
                        reinterpret_cast<const void*>(&k_gm_dist<8, true>),
                        reinterpret_cast<const void*>(&k_gm_reweight),
                        reinterpret_cast<const void*>(&k_bulyan_select),
-                       reinterpret_cast<const void*>(&k_bulyan_mean<8, 1, true>)};
+                       reinterpret_cast<const void*>(&k_bulyan_mean<8, 1, true>),
+                       reinterpret_cast<const void*>(&k_dnc_sqdist<8, true>),
+                       reinterpret_cast<const void*>(&k_dnc_select)};
   for (const void* fn : fns)
     if (hipFuncGetAttributes(&attr, fn) != hipSuccess) return 1;
   return 0;

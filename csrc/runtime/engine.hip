@@ -1123,6 +1123,51 @@ int myfyp_bulyan_mean_multi(const uint64_t* outs, int P, const uint64_t* srcs, i
   CHECK_HIP(hipGetLastError());
   return 0;
 }
+// DnC spectral filtering (fl_dnc): iters iterations (1..8) of subsampled distances, screening, the
+// top eigenpair of the centred Gram matrix and the removal of the m highest scores (iters * m < K),
+// then, with P > 0, out rows <- sum_k coef[k] * row k over the rows every iteration kept. w_host,
+// keys_host[iters] and forced_host[iters] are HOST arrays; tile tau of iteration t is taken iff
+// splitmix64(keys[t] ^ tau) < thr or tau == forced[t], every tile with all_tiles != 0. Device outputs
+// dist[iters*K*K], score[iters*K], lam[iters] (double), removed[K] (int), coef[K] (float). work:
+// iters * myfyp_krum_grid(n, K) * K(K-1)/2 floats. Enqueues only; K == 1 enqueues the mean alone, from
+// the coef the caller stored.
+int myfyp_dnc_multi(const uint64_t* outs, int P, const uint64_t* srcs, const float* w_host, int K, int m, int iters, const uint64_t* keys_host,
+                    uint64_t thr, const uint64_t* forced_host, int all_tiles, int64_t n, float* work, double* dist, double* score, double* lam,
+                    int* removed, float* coef, void* stream) {
+  if (!rows_ok(K, "dnc") || (P != 0 && !rows_ok(P, "dnc outputs"))) return 2;
+  if (n < 1 || srcs == nullptr || (P > 0 && outs == nullptr) || w_host == nullptr || dist == nullptr || score == nullptr || lam == nullptr ||
+      removed == nullptr || coef == nullptr || (K > 1 && work == nullptr)) {
+    g_last_error = "dnc: n >= 1 and the row tables, the weights and the work / dist / score / lam / removed / coef buffers are required";
+    return 2;
+  }
+  if (iters < 1 || iters > DNC_MAX_ITERS || m < 0 || (int64_t)iters * m >= K) {
+    g_last_error = "dnc: 1 <= iters <= 8, m >= 0 and iters * m < K (got K = " + std::to_string(K) + ", m = " + std::to_string(m) +
+                   ", iters = " + std::to_string(iters) + ")";
+    return 2;
+  }
+  if (!all_tiles && (keys_host == nullptr || forced_host == nullptr)) {
+    g_last_error = "dnc: a subsample needs the keys and the forced tiles";
+    return 2;
+  }
+  RowPtrs rows{};
+  OutPtrs o{};
+  RowW ww{};
+  DncTiles tiles{};
+  for (int k = 0; k < K; ++k) {
+    rows.p[k] = reinterpret_cast<const float*>(srcs[k]);
+    ww.w[k] = w_host[k];
+  }
+  for (int p = 0; p < P; ++p) o.p[p] = reinterpret_cast<float*>(outs[p]);
+  for (int t = 0; t < iters && !all_tiles; ++t) {
+    tiles.key[t] = keys_host[t];
+    tiles.forced[t] = forced_host[t];
+  }
+  tiles.thr = thr;
+  tiles.all = all_tiles ? 1 : 0;
+  fl_dnc(work, o, P, rows, ww, K, m, iters, tiles, n, dist, score, lam, removed, coef, (hipStream_t)stream);
+  CHECK_HIP(hipGetLastError());
+  return 0;
+}
 // Floats of the workspace of myfyp_geomed_multi for n coordinates of K rows.
 int64_t myfyp_geomed_work(int64_t n, int K) { return fl_geomed_work(n, K); }
 // Geometric median (smoothed Weiszfeld, iters steps; device outputs coef[K]: float, dist[K] and

@@ -3,8 +3,9 @@
 # Rows: no attack is not run; the three single-peer attacks of the FYP harness (sign flip, Gaussian
 # noise, scaling: one peer poisons every model it contributes, the first of the attackers) and the
 # four colluding attacks (ALIE, IPM, min-max, min-sum: every attacker sends one row crafted from the
-# honest peers' models of the round, fault_injection.ColludingAttack). Columns: FedAvg and the four
-# defences that aggregate on the device. Bulyan needs K >= 4f + 3 models, so with 8 peers it faces
+# honest peers' models of the round, fault_injection.ColludingAttack). Columns: FedAvg and the five
+# defences that aggregate on the device, DnC (the spectral defence min-max and min-sum were designed
+# against) last. Bulyan needs K >= 4f + 3 models, so with 8 peers it faces
 # one attacker where the others face two.
 
 import argparse
@@ -19,7 +20,7 @@ from myfyp_amd.utils.utils import set_test_settings  # noqa: E402
 SINGLE = ("sign_flip", "gaussian_noise", "scale")
 COLLUDING = ("alie", "ipm", "min_max", "min_sum")
 ATTACKS = SINGLE + COLLUDING
-AGGREGATORS = ("FedAvg", "Krum", "TrimmedMean", "GeometricMedian", "Bulyan")
+AGGREGATORS = ("FedAvg", "Krum", "TrimmedMean", "GeometricMedian", "Bulyan", "DnC")
 
 
 def attackers_for(aggregator: str, nodes: int, attackers: int) -> int:
@@ -28,7 +29,8 @@ def attackers_for(aggregator: str, nodes: int, attackers: int) -> int:
 
 
 def aggregator_spec(name: str, nodes: int, f: int) -> dict:
-    params = {"Krum": {"num_byzantine": f}, "Bulyan": {"num_byzantine": f}, "TrimmedMean": {"beta": f / nodes}}.get(name, {})
+    params = {"Krum": {"num_byzantine": f}, "Bulyan": {"num_byzantine": f}, "DnC": {"num_byzantine": f},
+              "TrimmedMean": {"beta": f / nodes}}.get(name, {})
     return {"name": name, "params": params}
 
 

@@ -1,7 +1,7 @@
 """MNIST MLP federated experiment: n nodes, r rounds, e epochs over memory/grpc/unix/collective protocols."""
 
 # Parity: p2pfl/examples/mnist.py:73-255 (same flags; adds --aggregator fedmedian/fedprox/krum/
-# trimmedmean/geomedian/bulyan, --batch_size, --dataset synthetic|huggingface, collective protocol). matplotlib
+# trimmedmean/geomedian/bulyan/dnc, --batch_size, --dataset synthetic|huggingface, collective protocol). matplotlib
 # plots are written to --plot_dir instead of plt.show(); --profiling uses cProfile (yappi is not
 # available) and writes one pstat per run under profile/mnist/<uuid>/.
 
@@ -30,7 +30,7 @@ def _parse_args() -> argparse.Namespace:
     p.add_argument("--token", type=str, default="", help="The API token for the Web Logger.")
     p.add_argument("--protocol", type=str, default="memory", choices=["grpc", "unix", "memory", "collective"])
     p.add_argument("--framework", type=str, default="pytorch", choices=["pytorch", "rocm"])
-    p.add_argument("--aggregator", type=str, default="fedavg", choices=["fedavg", "scaffold", "fedmedian", "fedprox", "krum", "trimmedmean", "geomedian", "bulyan"])
+    p.add_argument("--aggregator", type=str, default="fedavg", choices=["fedavg", "scaffold", "fedmedian", "fedprox", "krum", "trimmedmean", "geomedian", "bulyan", "dnc"])
     p.add_argument("--profiling", action="store_true", default=False, help="Enable profiling (cProfile).")
     p.add_argument("--reduced_dataset", action="store_true", default=False, help="Use a reduced dataset (nodes*50 partitions).")
     p.add_argument("--use_scaffold", action="store_true", default=False, help="Use the Scaffold aggregator.")

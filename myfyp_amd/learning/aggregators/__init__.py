@@ -1,8 +1,9 @@
-"""Aggregators: FedAvg, FedMedian, SCAFFOLD, FedProx, robust (Krum, trimmed mean, geometric median, Bulyan), decentralised NeighborAvg and its robust form ClippedGossip."""
+"""Aggregators: FedAvg, FedMedian, SCAFFOLD, FedProx, robust (Krum, trimmed mean, geometric median, Bulyan, DnC), decentralised NeighborAvg and its robust form ClippedGossip."""
 
 from myfyp_amd.learning.aggregators.aggregator import Aggregator, NoModelsToAggregateError
 from myfyp_amd.learning.aggregators.bulyan import Bulyan
 from myfyp_amd.learning.aggregators.clipped_gossip import ClippedGossip
+from myfyp_amd.learning.aggregators.dnc import DnC
 from myfyp_amd.learning.aggregators.fedavg import FedAvg
 from myfyp_amd.learning.aggregators.fedmedian import FedMedian
 from myfyp_amd.learning.aggregators.fedprox import FedProx
@@ -12,4 +13,4 @@ from myfyp_amd.learning.aggregators.neighbor_avg import NeighborAvg
 from myfyp_amd.learning.aggregators.scaffold import Scaffold
 from myfyp_amd.learning.aggregators.trimmed_mean import TrimmedMean
 
-__all__ = ["Aggregator", "NoModelsToAggregateError", "Bulyan", "ClippedGossip", "FedAvg", "FedMedian", "FedProx", "GeometricMedian", "Krum", "NeighborAvg", "Scaffold", "TrimmedMean"]
+__all__ = ["Aggregator", "NoModelsToAggregateError", "Bulyan", "ClippedGossip", "DnC", "FedAvg", "FedMedian", "FedProx", "GeometricMedian", "Krum", "NeighborAvg", "Scaffold", "TrimmedMean"]

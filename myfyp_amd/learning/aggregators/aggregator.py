@@ -14,7 +14,8 @@ topology mixing, ``"scaffold"`` → packed all-reduce + apply, ``"median"`` / ``
 all-gather + per-coordinate sorting-network kernel, ``"krum"`` → all-gather + distance, selection
 and weighted-mean kernels, ``"geometric_median"`` → all-gather + distance, reweighting and
 weighted-mean kernels, ``"bulyan"`` → all-gather + distance, iterated-selection and
-closest-to-the-median kernels, ``None`` → host fallback over gathered wire models).
+closest-to-the-median kernels, ``"dnc"`` → all-gather + subsampled-distance, spectral-filter and
+weighted-mean kernels, ``None`` → host fallback over gathered wire models).
 """
 
 from __future__ import annotations

@@ -19,6 +19,10 @@ Ops
 * ``bulyan_into`` — Bulyan: Krum's distances, θ = K − 2f rows picked by iterated Krum, then per
   coordinate the mean of the K − 4f picked values closest to their median, all on the device
   (K ≤ 16); returns ``(dist, score, coef, pick)``
+* ``dnc_into`` — DnC spectral filtering: per iteration Krum's distances over a subsample of the
+  coordinates, the top eigenpair of the centred Gram matrix ``−½·J·D·J``, the rows of largest
+  projection removed, then the weighted mean of the rows kept, all on the device (K ≤ 16); returns
+  ``(dist, score, lam, removed, coef)``
 * ``clipped_gossip_into`` — ClippedGossip: Krum's distances, per row a clipping radius and the
   clipped neighbour weights, then the mix in place, all on the device (K ≤ 16); returns
   ``(dist, tau, w_eff)``
@@ -48,6 +52,7 @@ __all__ = [
     "krum_into",
     "geometric_median_into",
     "bulyan_into",
+    "dnc_into",
     "clipped_gossip_into",
     "collude_into",
     "alie_z",
@@ -517,6 +522,229 @@ def bulyan_into(rows: Sequence[torch.Tensor], outs: Sequence[torch.Tensor], f: i
     if outs:
         _bulyan_stage2([rows[i] for i in range(k) if picks[i] >= 0], outs, k, f)
     return dist.to(dev), score.to(dev), coef.to(dev), pick.to(dev)
+
+
+DNC_MAX_ITERS = 8
+DNC_TILE = 256  # coordinates per subsample tile: one wave's 64 float4 groups
+DNC_SQUARINGS = 20
+_M64 = (1 << 64) - 1
+
+
+def splitmix64(x: int) -> int:
+    """``splitmix64`` of ``fl_ops.hip`` on a Python int (mod 2^64)."""
+    x = (x + 0x9E3779B97F4A7C15) & _M64
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _M64
+    return x ^ (x >> 31)
+
+
+def dnc_check(k: int, f, filter_frac, iters, subsample_dims) -> int:
+    """The parameters of a DnC call, checked; returns ``m = ceil(filter_frac · f)``, the rows one
+    iteration removes. Valid: ``f`` an integer >= 0, ``filter_frac`` finite and >= 0, ``1 <= iters
+    <= 8``, ``subsample_dims`` None or an integer >= 1, and ``iters · m < K``."""
+    import math
+
+    if isinstance(f, bool) or int(f) != f or f < 0:
+        raise ValueError(f"DnC: the attacker bound f must be an integer >= 0, got f = {f} (K = {k})")
+    ff = float(filter_frac)
+    if not math.isfinite(ff) or ff < 0:
+        raise ValueError(f"DnC: filter_frac must be finite and >= 0, got {filter_frac}")
+    if isinstance(iters, bool) or int(iters) != iters or not 1 <= iters <= DNC_MAX_ITERS:
+        raise ValueError(f"DnC: iters must be an integer in [1, {DNC_MAX_ITERS}], got {iters}")
+    if subsample_dims is not None and (isinstance(subsample_dims, bool) or int(subsample_dims) != subsample_dims or subsample_dims < 1):
+        raise ValueError(f"DnC: subsample_dims must be None or an integer >= 1, got {subsample_dims}")
+    m = int(math.ceil(ff * int(f)))
+    if k < 1 or int(iters) * m >= k:
+        raise ValueError(f"DnC needs iters · m < K models: K = {k}, iters = {iters}, m = ceil({filter_frac} · {f}) = {m}")
+    return m
+
+
+def _dnc_keys(n: int, seed: int, round: int, iters: int, subsample_dims):
+    """``(all_tiles, keys, thr, forced)`` of :func:`dnc_tiles`, without the masks."""
+    tiles = (int(n) + DNC_TILE - 1) // DNC_TILE
+    if subsample_dims is None or n <= subsample_dims:
+        return True, [0] * iters, _M64, [0] * iters
+    thr = min(_M64, (int(subsample_dims) << 64) // int(n))
+    kr = splitmix64(splitmix64(int(seed) & _M64) ^ (int(round) & _M64))
+    keys = [splitmix64(kr ^ t) for t in range(iters)]
+    forced = [splitmix64(kt ^ _M64) % tiles for kt in keys]
+    return False, keys, thr, forced
+
+
+def dnc_tiles(n: int, seed: int, round: int, iters: int, subsample_dims):
+    """The coordinate subsample of a DnC call over rows of length ``n``: per iteration t the tiles of
+    256 consecutive coordinates that enter the distances. ``T = ceil(n / 256)`` tiles. With
+    ``subsample_dims`` None or ``n <= subsample_dims`` every tile is taken and nothing is hashed
+    (keys and forced tiles 0, thr 2^64 − 1). Otherwise ``thr = min(2^64 − 1, floor(subsample_dims ·
+    2^64 / n))`` (the quotient taken in integers), ``k_r = sm(sm(seed) ^ round)``, ``k_t = sm(k_r ^
+    t)`` and tile τ is taken iff ``sm(k_t ^ τ) < thr`` or ``τ == sm(k_t ^ (2^64 − 1)) mod T``: one
+    tile is forced, so no iteration is empty. Returns ``(keys [iters], thr, forced [iters], mask
+    [iters, T] bool)``."""
+    import numpy as np
+
+    tiles = (int(n) + DNC_TILE - 1) // DNC_TILE
+    every, keys, thr, forced = _dnc_keys(n, seed, round, iters, subsample_dims)
+    mask = np.ones((iters, tiles), dtype=bool)
+    if not every:
+        with np.errstate(over="ignore"):
+            for t in range(iters):
+                x = np.arange(tiles, dtype=np.uint64) ^ np.uint64(keys[t])
+                x = x + np.uint64(0x9E3779B97F4A7C15)
+                x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+                x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+                x = x ^ (x >> np.uint64(31))
+                mask[t] = x < np.uint64(thr)
+                mask[t, forced[t]] = True
+    return keys, thr, forced, mask
+
+
+def dnc_select(dist, weights, m: int):
+    """Steps 1–5 of DnC on squared distances ``dist [iters, K, K]`` (or ``[K, K]``: one iteration),
+    in float64 on the host, as ``k_dnc_select`` does them. Per iteration:
+
+    1. screen: row i when more than half of its K − 1 distances are non-finite; then, j ascending,
+       an unscreened row j with a non-finite distance to an unscreened row i < j. V: the others.
+    2. centre: ``G = −½·J·D_V·J`` (row means, then their mean, then symmetrised); ``K_v <= 1`` or
+       ``tr G <= 0``: λ = 0 and every score on V is 0.
+    3. ``M = G / tr G``; 20 times ``M <- M·M`` (inner index ascending), ``M <- M / tr M``;
+       ``j* = argmax M_jj`` (the lowest on a tie), ``u = M[:, j*] / |M[:, j*]|``, ``λ = uᵀGu``,
+       ``s_i = λ·u_i²``; a screened row scores +inf.
+    4. the m highest scores are removed, the higher row first among equals; screened rows always.
+    5. a row is kept iff every iteration keeps it: ``coef_k = float32(w_k / Σ_kept w)``, 0 for the
+       others; nothing kept: ``w / Σ w`` over all rows.
+
+    Returns ``(score [iters, K] float64, lam [iters] float64, removed [K] int32: the first iteration
+    that removed the row or −1, coef [K] float32)`` as numpy arrays."""
+    import numpy as np
+
+    d_all = np.asarray(dist, dtype=np.float64)
+    if d_all.ndim == 2:
+        d_all = d_all[None]
+    iters, k = d_all.shape[0], d_all.shape[1]
+    score = np.zeros((iters, k))
+    lam = np.zeros(iters)
+    removed = np.full(k, -1, dtype=np.int32)
+    with np.errstate(all="ignore"):
+        for it in range(iters):
+            d = d_all[it]
+            fin = np.isfinite(d)
+            scr = [2 * sum(1 for b in range(k) if b != a and not fin[a, b]) > k - 1 for a in range(k)]
+            for b in range(1, k):
+                if not scr[b] and any(not scr[a] and not fin[a, b] for a in range(b)):
+                    scr[b] = True
+            v = [a for a in range(k) if not scr[a]]
+            kv = len(v)
+            s = np.zeros(k)
+            if kv > 1:
+                dv = d[np.ix_(v, v)]
+                r = np.array([sum(float(x) for x in row) for row in dv]) / kv
+                c = sum(float(x) for x in r) / kv
+                a_ = -0.5 * (((dv - r[:, None]) - r[None, :]) + c)
+                g = 0.5 * (a_ + a_.T)
+                tr = sum(float(g[q, q]) for q in range(kv))
+                if tr > 0.0:
+                    mm = g / tr
+                    for _ in range(DNC_SQUARINGS):
+                        acc = np.zeros_like(mm)
+                        for q in range(kv):
+                            acc = acc + mm[:, q : q + 1] * mm[q : q + 1, :]
+                        mm = acc / sum(float(acc[q, q]) for q in range(kv))
+                    js = int(np.argmax(np.diag(mm)))
+                    col = mm[:, js]
+                    u = col / np.sqrt(sum(float(x) * float(x) for x in col))
+                    lam[it] = float(u @ (g @ u))
+                    s[v] = lam[it] * u * u
+            s[[a for a in range(k) if scr[a]]] = np.inf
+            score[it] = s
+            order = sorted(range(k), key=lambda a: (-s[a], -a))
+            for a in range(k):
+                if (scr[a] or a in order[: int(m)]) and removed[a] < 0:
+                    removed[a] = it
+    w = np.array([float(x) for x in weights], dtype=np.float64)
+    kept = removed < 0
+    coef = np.zeros(k)
+    if not kept.any():
+        coef = w / w.sum() if w.sum() > 0 else np.full(k, 1.0 / k)
+    else:
+        ws = float(sum(w[a] for a in range(k) if kept[a]))
+        coef[kept] = w[kept] / ws if ws > 0 else 1.0 / int(kept.sum())
+    return score, lam, removed, coef.astype(np.float32)
+
+
+def dnc_into(rows: Sequence[torch.Tensor], outs: Sequence[torch.Tensor], weights: Sequence[float], f: int, filter_frac: float = 1.0, iters: int = 1,
+             subsample_dims: Optional[int] = 10000, seed: int = 0, round: int = 0):
+    """Divide-and-Conquer (DnC; Shejwalkar & Houmansadr, NDSS 2021) over 1-D fp32 rows with at most
+    ``f`` attackers: ``iters`` times, on a fresh subsample of the coordinates (:func:`dnc_tiles`), the
+    squared distances from differences, then :func:`dnc_select` — the rows' projections on the top
+    singular direction of the centred model matrix, read off the K × K centred Gram matrix
+    ``−½·J·D·J``, and the ``m = ceil(filter_frac · f)`` largest removed. ``outs[p] = Σ_k coef[k]·
+    rows[k]`` over the rows every iteration kept, ``coef[k] = w_k / Σ_kept w``. ``f == 0`` gives the
+    sample-weighted mean. A row with NaN / Inf coordinates spoils only its own distances: it is
+    screened and removed. Returns ``(dist [iters, K, K] float64, score [iters, K] float64, lam [iters]
+    float64, removed [K] int32, coef [K] float32)`` on the rows' device; ``outs=[]`` gives the
+    selection only.
+
+    Deviation from the paper: the subsample is Bernoulli per tile of 256 coordinates (plus one
+    forced tile), not exactly ``subsample_dims`` coordinates.
+
+    On the GPU (K <= 16 rows, <= 16 outputs, which may alias the rows) it is three launches —
+    ``k_dnc_sqdist<K>``, ``k_dnc_select``, ``k_coef_mean<K>`` — that only enqueue (K == 1: the mean
+    alone). Elsewhere: float64 torch math (the oracle)."""
+    import numpy as np
+
+    k = len(rows)
+    if len(weights) != k:
+        raise ValueError(f"{k} rows but {len(weights)} weights")
+    m = dnc_check(k, f, filter_frac, iters, subsample_dims)
+    iters = int(iters)
+    dev = rows[0].device
+    n = rows[0].numel()
+    if n < 1 or any(t.numel() != n for t in [*rows, *outs]):
+        raise ValueError(f"DnC: rows and outputs must share one length >= 1, got {[t.numel() for t in [*rows, *outs]]}")
+    if _native_rows(rows, outs):
+        lib = _lib()
+        every, keys, thr, forced = _dnc_keys(n, seed, round, iters, subsample_dims)
+        work = torch.empty(max(1, iters * int(lib.myfyp_krum_grid(n, k)) * (k * (k - 1) // 2)), dtype=torch.float32, device=dev)
+        if k == 1:  # no pair, no selection launch: the one row is the result
+            dist = torch.zeros(iters, 1, 1, dtype=torch.float64, device=dev)
+            score = torch.zeros(iters, 1, dtype=torch.float64, device=dev)
+            lam = torch.zeros(iters, dtype=torch.float64, device=dev)
+            removed = torch.full((1,), -1, dtype=torch.int32, device=dev)
+            coef = torch.ones(1, dtype=torch.float32, device=dev)
+        else:
+            dist = torch.empty(iters, k, k, dtype=torch.float64, device=dev)
+            score = torch.empty(iters, k, dtype=torch.float64, device=dev)
+            lam = torch.empty(iters, dtype=torch.float64, device=dev)
+            removed = torch.empty(k, dtype=torch.int32, device=dev)
+            coef = torch.empty(k, dtype=torch.float32, device=dev)
+        src, keep_s = _host_ptrs(rows)
+        dst, keep_d = _host_ptrs(outs)
+        w = (ctypes.c_float * k)(*[float(x) for x in weights])
+        ka = (ctypes.c_uint64 * iters)(*keys)
+        fa = (ctypes.c_uint64 * iters)(*forced)
+        _native.check(lib.myfyp_dnc_multi(dst, len(outs), src, ctypes.cast(w, ctypes.c_void_p), k, m, iters, ctypes.cast(ka, ctypes.c_void_p), thr,
+                                          ctypes.cast(fa, ctypes.c_void_p), int(every), n, work.data_ptr(), dist.data_ptr(), score.data_ptr(),
+                                          lam.data_ptr(), removed.data_ptr(), coef.data_ptr(), _stream()), "dnc_multi")
+        return dist, score, lam, removed, coef
+    _, _, _, mask = dnc_tiles(n, seed, round, iters, subsample_dims)
+    x = torch.stack([r.detach().double().reshape(-1) for r in rows])
+    dist = torch.zeros(iters, k, k, dtype=torch.float64)
+    for t in range(iters):
+        take = torch.from_numpy(np.repeat(mask[t], DNC_TILE)[:n]).to(x.device)
+        xt = x[:, take]
+        for i in range(k):
+            for j in range(i + 1, k):
+                dist[t, i, j] = dist[t, j, i] = float((xt[i] - xt[j]).square().sum())
+    score, lam, removed, coef = dnc_select(dist.numpy(), weights, m)
+    if outs:
+        mean = torch.zeros(n, dtype=torch.float64, device=x.device)
+        for i in range(k):
+            if coef[i] != 0:
+                mean += float(coef[i]) * x[i]
+        for o in outs:
+            o.copy_(mean.view_as(o))
+    return (dist.to(dev), torch.from_numpy(score).to(dev), torch.from_numpy(lam).to(dev), torch.from_numpy(removed).to(dev),
+            torch.from_numpy(coef).to(dev))
 
 
 GEOMED_MAX_ITERS = 32

@@ -45,6 +45,8 @@ _SIGNATURES = {
     "myfyp_krum_multi": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "myfyp_bulyan_multi": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "myfyp_bulyan_mean_multi": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p]),
+    "myfyp_dnc_multi": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, ctypes.c_uint64, c_void_p, c_int, c_int64, c_void_p,
+                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "myfyp_clipped_gossip": (c_int, [c_void_p, c_int, c_void_p, c_int, ctypes.c_double, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "myfyp_geomed_work": (c_int64, [c_int64, c_int]),
     "myfyp_geomed_multi": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, ctypes.c_double, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

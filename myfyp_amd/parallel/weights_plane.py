@@ -791,7 +791,7 @@ def _publish_clipping(fed: Federation, aggregator, clipping, addrs=None) -> None
 
 
 # aggregator kinds reduced on the device (no wire models, no host copies)
-DEVICE_KINDS = ("mean", "neighbor", "scaffold", "median", "krum", "trimmed_mean", "geometric_median", "bulyan")
+DEVICE_KINDS = ("mean", "neighbor", "scaffold", "median", "krum", "trimmed_mean", "geometric_median", "bulyan", "dnc")
 
 
 def _scaffold_cb(learner):
@@ -1061,6 +1061,33 @@ def aggregate_bulyan(fed: Federation, arrived: Dict[str, Tuple[float, Any]], agg
     fed.record("aggregate", time.perf_counter() - t0)
 
 
+@traced("aggregate_dnc")
+def aggregate_dnc(fed: Federation, arrived: Dict[str, Tuple[float, Any]], aggregator, round_: int) -> None:
+    """DnC spectral filtering over the trainers' models on the device (host math: ``DnC.aggregate``):
+    the all-gather of :func:`aggregate_median`, then ``ops.dnc_into`` — per iteration the distances
+    over the coordinate subsample of ``(seed, round_, iteration)``, the top eigenpair of the centred
+    Gram matrix and the rows of largest projection removed, then the sample-weighted mean of the
+    rows kept written into every local peer, the selection never leaving the device on the round's
+    path. ``round_`` is stored as ``aggregator.round`` on the aggregator given and on every local
+    node's aggregator, so all ranks draw the same subsample. Bad parameters (``iters · m >= K`` with K
+    this round's trainers) raise ``ValueError`` on every rank, before any collective. Every rank
+    reduces the same gathered buffer with the same grid, so all of them remove the same peers, bit
+    for bit. Afterwards every local node's aggregator carries ``last_selection = (trainer addresses
+    in row order, coef)``; ``coef`` is the device tensor (reading it is the caller's
+    synchronisation), 0 for a removed peer."""
+    t0 = time.perf_counter()
+    aggregator.round = int(round_)
+    for node in fed.local_nodes.values():
+        if getattr(node.aggregator, "collective_kind", None) == "dnc":
+            node.aggregator.round = int(round_)
+    fed.run_aggregation(lambda: _robust(fed, arrived, aggregator, "dnc"))
+    fed.record("aggregate", time.perf_counter() - t0)
+
+
+def _dnc_check(aggregator, k: int) -> None:
+    ops.dnc_check(k, aggregator.f, aggregator.filter_frac, aggregator.iters, aggregator.subsample_dims)
+
+
 def _trim_count(aggregator, k: int) -> int:
     trim = int(np.floor(aggregator.beta * k))
     if 2 * trim >= k:
@@ -1078,6 +1105,9 @@ def _robust_into(kind: str, aggregator, rows, outs, ws):
             return ops.geometric_median_into(rows, outs, ws, aggregator.iters, aggregator.nu)[0]
         if kind == "bulyan":
             return ops.bulyan_into(rows, outs, aggregator.f)[2]
+        if kind == "dnc":
+            return ops.dnc_into(rows, outs, ws, aggregator.f, aggregator.filter_frac, aggregator.iters, aggregator.subsample_dims, aggregator.seed,
+                                aggregator.round)[4]
         return ops.krum_into(rows, outs, ws, aggregator.f, aggregator.m)[2]
 
 
@@ -1092,8 +1122,8 @@ def _row_fns(learners, kind: str):
     ``get_parameters()`` — the whole ``state_dict``, BatchNorm's integer ``num_batches_tracked``
     included — so the Krum row carries those counters too, behind everything that is unpacked: the
     device and the host then score the same vector and select the same peers. The geometric median
-    and Bulyan measure distances too, and take the same rows."""
-    whole = kind in ("krum", "geometric_median", "bulyan")
+    Bulyan and DnC measure distances too, and take the same rows."""
+    whole = kind in ("krum", "geometric_median", "bulyan", "dnc")
     live = all(len(state_tensors(lr)) == 1 and not (whole and _int_buffers(lr)) for lr in learners)
     if live:
         return True, lambda lr: lr.flat_params()
@@ -1105,7 +1135,7 @@ def _row_fns(learners, kind: str):
 def _publish_selection(fed: Federation, addrs, aggregator, order, coef) -> None:
     if coef is None:
         return
-    # Krum and Bulyan publish a selection, the geometric median its weights
+    # Krum, Bulyan and DnC publish a selection, the geometric median its weights
     attr = "last_weights" if getattr(aggregator, "collective_kind", None) == "geometric_median" else "last_selection"
     setattr(aggregator, attr, (list(order), coef))
     for a in addrs:
@@ -1134,6 +1164,8 @@ def _robust(fed: Federation, arrived: Dict[str, Tuple[float, Any]], aggregator, 
         _trim_count(aggregator, len(order))  # the same K on every rank: all of them raise, or none
     if kind == "bulyan":
         ops.bulyan_check(len(order), aggregator.f)  # likewise
+    if kind == "dnc":
+        _dnc_check(aggregator, len(order))  # likewise
     live, row_of = _row_fns(list(learners.values()), kind)
 
     def reduce_rows(rows) -> None:
@@ -1178,6 +1210,8 @@ def _mesh_robust(fed: Federation, arrived: Dict[str, Tuple[float, Any]], aggrega
         _trim_count(aggregator, len(order))
     if kind == "bulyan":
         ops.bulyan_check(len(order), aggregator.f)
+    if kind == "dnc":
+        _dnc_check(aggregator, len(order))
     _, row_of = _row_fns(learners, kind)
     kmax = max(counts)
     n = row_of(learners[0]).numel()

@@ -24,7 +24,7 @@ One description drives every experiment the examples, the CLI and the FYP harnes
         name: MLP               # MLP | LeNet5 | ResNet18, or package + model_build_fn
         params: {}              # + compression: {ptq: {dtype: float16}, topk: {k: 0.1}, zlib: {level: 6}}
       aggregator:
-        name: FedAvg            # FedAvg | FedMedian | Scaffold | FedProx | Krum | TrimmedMean | GeometricMedian | Bulyan | NeighborAvg | ClippedGossip
+        name: FedAvg            # FedAvg | FedMedian | Scaffold | FedProx | Krum | TrimmedMean | GeometricMedian | Bulyan | DnC | NeighborAvg | ClippedGossip
         params: {}
       attack: {node: 1, kind: sign_flip, sigma: 0.1, persistent: false}
       # or colluding attackers (collective protocol only): {kind: min_max, nodes: [1, 5], z: 1.0, eps: 0.5}
@@ -72,6 +72,7 @@ _AGGREGATORS = {
     "geometricmedian": ("myfyp_amd.learning.aggregators.geometric_median", "GeometricMedian"),
     "geomedian": ("myfyp_amd.learning.aggregators.geometric_median", "GeometricMedian"),
     "bulyan": ("myfyp_amd.learning.aggregators.bulyan", "Bulyan"),
+    "dnc": ("myfyp_amd.learning.aggregators.dnc", "DnC"),
     "neighboravg": ("myfyp_amd.learning.aggregators.neighbor_avg", "NeighborAvg"),
     "clippedgossip": ("myfyp_amd.learning.aggregators.clipped_gossip", "ClippedGossip"),
 }

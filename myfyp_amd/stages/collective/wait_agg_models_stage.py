@@ -54,6 +54,9 @@ def join_aggregation(state, learner, aggregator, trainer: bool) -> None:
         elif kind == "bulyan" and device_path:
             weights_plane.aggregate_bulyan(f, arrived, aggregator)
             extra = None
+        elif kind == "dnc" and device_path:
+            weights_plane.aggregate_dnc(f, arrived, aggregator, round_)
+            extra = None
         else:
             weights_plane.aggregate_generic(f, arrived, aggregator)
             extra = None
@@ -69,19 +72,19 @@ def join_aggregation(state, learner, aggregator, trainer: bool) -> None:
 
 
 # kinds whose device path the ranks vote on each round (the others always have one)
-_VOTED_KINDS = ("scaffold", "median", "trimmed_mean", "krum", "geometric_median", "bulyan")
+_VOTED_KINDS = ("scaffold", "median", "trimmed_mean", "krum", "geometric_median", "bulyan", "dnc")
 
 
 def _agree_device_path(f, kind: str, arrived) -> bool:
-    """SCAFFOLD / FedMedian / TrimmedMean / Krum / GeometricMedian / Bulyan reduce on the device only when EVERY rank's peers
+    """SCAFFOLD / FedMedian / TrimmedMean / Krum / GeometricMedian / Bulyan / DnC reduce on the device only when EVERY rank's peers
     are device learners (flat parameter buffers): the ranks agree on it through one control-plane
     gather, so all of them issue the same collectives (a rank whose local peers happen to be
-    non-trainers cannot tell from its own, empty, payloads). The trimmed-mean, Krum, geometric-median and Bulyan kernels take
+    non-trainers cannot tell from its own, empty, payloads). The trimmed-mean, Krum, geometric-median, Bulyan and DnC kernels take
     at most ``ROBUST_MAX_ROWS`` rows: the gather also carries every rank's trainer count, and more
     trainers than that in the round send every rank to the generic path."""
     local = [a for a in arrived if a in f.local_nodes]
     local_ok = all(hasattr(f.local_nodes[a].learner, "flat_params") for a in local)
-    if kind not in ("trimmed_mean", "krum", "geometric_median", "bulyan"):
+    if kind not in ("trimmed_mean", "krum", "geometric_median", "bulyan", "dnc"):
         return all(f.all_gather_object(bool(local_ok)))
     votes = f.all_gather_object((bool(local_ok), sum(1 for a in local if arrived[a][0] > 0)))
     return all(ok for ok, _ in votes) and sum(c for _, c in votes) <= weights_plane.ROBUST_MAX_ROWS
