@@ -806,6 +806,9 @@ static hipError_t prepare_one(int lds) {
 
 hipError_t mlp_persistent_prepare(const MLPArgs& a) {
   const int lds = (int)persistent_lds(a);
+  // beyond the LDS limit the kernel is never launched (mlp_persistent_supported); asking the runtime
+  // for that much would fail and leave its error behind for the caller's next runtime call
+  if (lds > 160 * 1024) return hipErrorInvalidValue;
   hipError_t e = a.Bpad == 64 ? prepare_one<64, true>(lds) : prepare_one<32, true>(lds);
   if (e != hipSuccess) return e;
   return a.Bpad == 64 ? prepare_one<64, false>(lds) : prepare_one<32, false>(lds);

@@ -1351,6 +1351,9 @@ void* mlp_engine_create(int P, int D0, int D1, int D2, int D3, int B) {
       e->pb32.flags = (unsigned*)p;
       e->pb32.err = e->pb.err;
       if (mlp_persistent_f32_prepare(a) != hipSuccess) e->pb32.h1x = nullptr;
+      // a shape an epoch kernel cannot take (its LDS request refused) is served by the step path: that is
+      // no error, so it must not stay behind as the runtime's last error for the caller's next call
+      (void)hipGetLastError();
     }
   }
   if (rc) {

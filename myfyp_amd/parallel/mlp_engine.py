@@ -738,7 +738,8 @@ class MLPEngineHandle:
             D0 = self.group.dims[0]
             return torch.zeros(0, D0, dtype=torch.uint8, device=self.group.device), torch.zeros(0, dtype=torch.int32, device=self.group.device)
         x, y = self.learner.device_data(train, label_dtype=torch.int32)
-        x = x.reshape(x.shape[0], -1)
+        # (a split without rows: -1 is ambiguous for 0 elements)
+        x = x.reshape(x.shape[0], -1 if x.shape[0] else self.group.dims[0])
         if x.dtype != torch.uint8:
             raise TypeError("fused MLP engine expects uint8 images")
         if not x.is_contiguous():

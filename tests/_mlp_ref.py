@@ -668,6 +668,8 @@ FAITHFUL = 2.0 ** -23  # one fp32 ulp, relative: the bf16 MFMA's accumulation (s
 # 5e-4 for W2 at D0 = 40); with these factors every tensor's floor is below 1e-4 (asserted by
 # ``test_mlp_ref_cpu.py`` for every case of part (d)).
 RANDN32_SCALE = {"W1": 16.0, "W2": 0.125, "W3": 0.5, "b1": 2.0 ** -10, "b2": 2.0 ** -10, "b3": 2.0 ** -10}
+# ``randn16``: the same matrices with larger b2 and b3, for part (d) of the bf16 epoch kernel's tests (section below)
+RANDN16_SCALE = dict(RANDN32_SCALE, b2=2.0 ** -7, b3=2.0 ** -4)
 
 # The cases of tests/test_mlp_f32_oracle_gpu.py: shapes (D0, D3, B), layouts (gang layout, owner K split, the H1 / dH2
 # fragment switches), and the training rows of the two peers.
@@ -718,9 +720,10 @@ def case32(D0, D3, B, family, n, n_test=(4, 4), seed=0):
     training rows and ``n_test[p]`` test rows of the family's pixels, labels uniform in ``[0, D3)``."""
     D = dims32(D0, D3)
     g = torch.Generator().manual_seed(7 + 1000003 * seed + 7919 * D0 + 5 * D3 + B + 131 * n[0] + 257 * n[1] + 17 * sum(n_test) + sum(map(ord, family)))
-    W = _weights(g, D, "randn" if family == "randn32" else family)
-    if family == "randn32":
-        W = {k: v * RANDN32_SCALE[k] for k, v in W.items()}
+    scale = {"randn32": RANDN32_SCALE, "randn16": RANDN16_SCALE}.get(family)
+    W = _weights(g, D, "randn" if scale else family)
+    if scale:
+        W = {k: v * scale[k] for k, v in W.items()}
         family = "randn"
     c = dict(D=D, B=B, family=family, n=list(n), n_test=list(n_test), W=[{k: v[p] for k, v in W.items()} for p in range(2)])
     c["x"] = [_pixels(g, family, n[p], D0) for p in range(2)]
@@ -857,19 +860,20 @@ def adam_coeffs(hp, k):
     return R.f32(R.f32(hp["lr"]) / (1.0 - b1 ** k)), R.f32(1.0 / math.sqrt(1.0 - b2 ** k))
 
 
-def adam_w32(hp, w, m1, v1, k, bm=0.0, bv=0.0):
+def adam_w32(hp, w, m1, v1, k, bm=0.0, bv=0.0, coeffs=None):
     """The weight after ``upd32``'s Adam tail from the new moments ``m1``, ``v1`` (known to ``bm``, ``bv``) at step ``k``:
-    ``(w', bound)``."""
-    lr_t, inv = adam_coeffs(hp, k)
+    ``(w', bound)``. ``coeffs``: ``(lr_t, inv, relative bound of lr_t, of inv)`` where the kernel forms them otherwise than
+    ``persist::BiasCorr`` (:func:`adam_coeffs16`); the default is ``adam_coeffs`` trusted to one ulp each."""
+    lr_t, inv, r_lr, r_inv = coeffs if coeffs is not None else (*adam_coeffs(hp, k), 2 * U, 2 * U)
     eps = R.f32(EPS)
     sq = torch.sqrt(v1)
     d_sq = 2 * U * sq + torch.minimum(torch.sqrt(torch.as_tensor(bv, dtype=F64) + 0 * sq), torch.as_tensor(bv, dtype=F64) / sq.clamp_min(1e-300)) + 2.0 ** -60
     den = sq * inv + eps
-    d_den = inv * d_sq + 2 * U * sq * inv + U * den
+    d_den = inv * d_sq + r_inv * sq * inv + U * den
     q = m1 / den
     dq = bm / den + q.abs() * (d_den / den + 3 * U)
     w1 = w - lr_t * q
-    return w1, SECOND * (U * w1.abs() + lr_t * dq + 2 * U * lr_t * q.abs())
+    return w1, SECOND * (U * w1.abs() + lr_t * dq + r_lr * lr_t * q.abs())
 
 
 def upd32(hp, w, g, m, v, k, anchor=None, cg=None, cl=None, dg=0.0):
@@ -915,3 +919,230 @@ def upd32(hp, w, g, m, v, k, anchor=None, cg=None, cl=None, dg=0.0):
         w1 = w1 - hp["lr"] * e
         bw = bw + SECOND * (U * w1.abs() + hp["lr"] * U * e.abs())
     return w1, m1, v1, bw, bm, bv
+
+
+# ---------------------------------------------------------------------------------------------
+# the bf16 epoch kernel (mlp_persistent.hip, mlp_persistent_epoch<BP, ADAM>)
+# ---------------------------------------------------------------------------------------------
+# D1 = 256 and D2 = 128 are fixed there too. The model is :func:`step`'s (bf16 where the kernel stores bf16: the
+# matrices as the MFMA reads them, H1, H2, dlogits, dH2, dH1; the biases and every sum in fp32), per peer of a
+# ``case32``, with an INTERVAL for everything behind the fast softmax.
+#
+# Forward. On the ``exact`` / ``exact_tie`` family the matrices are bf16 values already and every term of the three
+# sums is a multiple of ``units(D)``'s grid; a bf16 rounding of a multiple of a power of two is one again, so the
+# rounded H1 and H2 stay on the grid. With ``sum |term| / unit < 2^24`` (:func:`grid_ratios16`) the kernel's fp32 sums
+# are exact however the 8 waves, the K steps and the MFMA split them: H1, H2, the logits, the relu masks and
+# the first maximum are the oracle's, bit for bit.
+#
+# dlogits. ``mlp_persistent_epoch``'s head forms ``logp`` and ``d = (__expf(logp) - onehot) / rows`` exactly as ``mlp_head``
+# does, so ``eps_sm`` of the module docstring holds unchanged: the fp32 ``d`` lies within ``e = eps_sm / rows`` of
+# ``(softmax - onehot) / rows``, and, rounding being monotone, the stored bf16 value lies in
+# ``[bf16(ref - e), bf16(ref + e)]``: one value for most elements, two neighbours where ``ref`` sits within ``e`` of a
+# rounding boundary (the element "straddles"). With one class ``__expf(0) = exp2(0) = 1`` and ``__logf(1) = 0``
+# exactly: ``d`` is an exact zero and the interval is ``[0, 0]``.
+#
+# dH2, dH1. ``dlogits W3`` has at most 16 terms, ``dH2 W2`` 128; on the grid of the finest bit of their own terms
+# (:func:`_iratio`, taken over both ends of each interval) ``sum |term| / unit < 2^24``, so these fp32 sums are exact
+# in any order as well, whichever value each upstream element took. An exact sum is monotone in each operand:
+# the sum lies between the sums of the ends chosen by the sign of the weight (:func:`_isum`), the mask is exact, the
+# bf16 rounding is monotone: ``dH2`` in ``[bf16(lo), bf16(hi)]``, and ``dH1`` from that in the same way.
+#
+# Gradients. The reference is the float64 sum over the batch of the products of the central values
+# (``bf16(ref)`` carried through). The kernel's operand differs from the central one by at most the interval's
+# width, so a gradient element's radius is ``sum_rows width[row] |other operand[row]|`` (nothing of second order: the
+# other operand is exact), plus ``gamma(Bpad) sum |term|`` for the fp32 sum over the batch (two chained 32-row MFMAs,
+# or Bpad scalar additions for db2 and db3, or 4 additions, two shuffles and up to four LDS atomics in arrival
+# order for db1: any tree of at most Bpad additions; the MFMA's own rounding, faithful only, is 2 u per
+# instruction and there are two at most). Where the element's own terms satisfy the exactness condition above
+# (the finest bit of any dH row times the finest bit of the other operand's column, both ends of the intervals
+# taken) that term is dropped: every order gives the same bits, the atomics of db1 included (elsewhere db1's
+# arrival order is inside ``gamma(Bpad) >= gamma(4)`` like any other order). :func:`bounds16`.
+#
+# Reading the gradient. One Adam step at ``lr = 0`` without weight decay from fresh state leaves ``m = fl(c1 g)`` with
+# ``c1 = 1 - beta1`` (exact in fp32, Sterbenz), ``v = fl(c2 fl(g g))`` and ``w`` bit-equal (``fma(-0, q, w)``): ``|m - c1 g_ref| <=
+# c1 radius + u |c1 g|``. ``v`` against the kernel's own ``m``: ``g = (m / c1)(1 + d)``, ``|d| <= u``, so ``v = c2 (m / c1)^2`` within
+# ``4 u`` relative (2 u from ``d``, the two product roundings) and an absolute 2^-125 where fp32 flushes.
+#
+# Bias correction. ``persist::bias_corr`` forms ``lr_t = lr / (1.f - __powf(beta1, k))`` and ``inv = 1.f / sqrtf(1.f -
+# __powf(beta2, k))`` in fp32. ``__powf`` is taken as good to one ulp, the figure this module already assumes for
+# ``v_exp_f32`` / ``v_log_f32`` (2 u relative): ``|b - beta^k| <= 2 u beta^k``. ``1 - b`` is exact for ``b >= 1/2`` and rounds once
+# otherwise, so ``1 - beta^k`` is off by ``r(beta) = 2 u beta^k / (1 - beta^k) + u`` relative: at k = 1 about
+# ``2 u beta2 / (1 - beta2) = 1.2e-4`` for beta2 and 18 u for beta1. The division rounds once (u): ``lr_t`` to ``r(beta1) + u``.
+# ``sqrtf`` is taken as 1 ulp (2 u) on a value off by ``r(beta2)``, half of which it passes on, and the division
+# rounds once: ``inv`` to ``r(beta2) / 2 + 3 u``. :func:`adam_coeffs16` returns both values, formed in double from the
+# fp32 betas, with these bounds; ``adam_w32`` carries them into the weight. They tell step k from step k + 1 easily:
+# at k = 20 ``lr_t`` changes by 1.4 % and ``inv`` by 2.4 % per step, the bounds are 4e-7 and 3e-6.
+#
+# Moments over several steps with the weights frozen: :func:`moments16`, the recursions ``m' = fma(b1, m, fl(c1 g))`` and
+# ``v' = fma(b2, v, fl(c2 fl(g g)))`` with ``g`` known to its radius ``dg``; unlike ``upd32``'s bound the one of ``v`` keeps ``dg^2``: a
+# radius here may be as large as the element itself (a gradient that cancels).
+BF16_SHAPES = [(784, 10, 32), (784, 10, 64), (40, 16, 24), (776, 16, 40), (264, 10, 48), (1024, 10, 32), (8, 1, 32)]
+BF16_MAIN = BF16_SHAPES[:2]
+BF16_ONE_STEP = {**F32_ONE_STEP, 40: [(1, 40), (2, 39)], 48: [(1, 48), (2, 33)]}
+BF16_STEPS = {**F32_STEPS, 40: [(70, 80), (100, 120), (170, 200)], 48: [(80, 96), (110, 144), (200, 240)]}
+BF16_LEARN = {**F32_LEARN, 40: (100, 190)}
+BF16_LEARN_SHAPES = [(784, 10, 64), (40, 16, 24), (776, 16, 40)]
+# Part (d): ``randn16`` weights at lr 2e-5. bf16 makes the epoch chaotic in places (a relu, a stored activation or
+# a shadow weight that rounds the other way moves a tensor by 1e-5 to 1e-2 of its update), and which of those a
+# correct implementation meets depends on its accumulation order. At this learning rate and with these bias
+# scales one term common to every fp32 implementation dominates the twin's floor of every tensor: the fp32
+# rounding of the master row after each update (floors 2e-5 to 4e-4). Case seed 0 of the two wide shapes
+# holds a near-tie that the twin itself takes the other way (floor 6e-3, over the cap): seed 1.
+BF16_LEARN_SEED = {(784, 10, 64): 1, (776, 16, 40): 1}
+BF16_LEARN_HP = {"sgd": dict(kind=1, lr=2e-5, momentum=0.0, wd=0.0, nesterov=False), "sgd_wd": dict(kind=1, lr=2e-5, momentum=0.0, wd=5e-4, nesterov=False)}
+BF16_OPT = {"sgd": dict(kind=1, lr=2.0 ** -6, momentum=0.0, wd=0.0, nesterov=False), "sgd_wd": dict(kind=1, lr=2.0 ** -6, momentum=0.0, wd=5e-4, nesterov=False),
+            "adam": dict(kind=0, lr=1e-3), "adam_wd": dict(kind=0, lr=1e-3, wd=1e-4)}
+BF16_OPT_CASE = ((784, 10, 64), (31, 33))  # part (b): the main shape, both peers a partial batch across the 32-row tile
+BF16_EDGE = ((784, 10, 32), (33, 150))  # part (e): 2 steps beside 5
+BF16_GANG = (40, 16, 24)  # part (e): 8 peers (4 cases of 2, the seeds below) and 9
+BF16_GANG_ROWS, BF16_GANG_SEEDS = (23, 24), (0, 1, 2, 3, 4)
+BF16_SEED = {(40, 16, 24, (1, 24)): 1}  # (D0, D3, B, n) -> case seed, where seed 0 misses a cap of test_mlp_ref_cpu.py
+
+
+def bf16_grid_cases():
+    """Every grid case of tests/test_mlp_bf16_epoch_oracle_gpu.py: ``(D0, D3, B, n, seed)``."""
+    out = []
+    for D0, D3, B in BF16_SHAPES:
+        pairs = list(BF16_ONE_STEP[B])
+        pairs += BF16_STEPS[B] if (D0, D3, B) in BF16_MAIN else BF16_STEPS[B][1:2]
+        out += [(D0, D3, B, n, BF16_SEED.get((D0, D3, B, n), 0)) for n in pairs]
+    out.append((*BF16_OPT_CASE[0], BF16_OPT_CASE[1], 0))
+    out.append((*BF16_EDGE[0], BF16_EDGE[1], 0))
+    out += [(*BF16_GANG, BF16_GANG_ROWS, s) for s in BF16_GANG_SEEDS]
+    return list(dict.fromkeys(out))
+
+
+def forward16(W, X):
+    H1 = fc(X, bf16(W["W1"]), W["b1"])
+    H2 = fc(H1, bf16(W["W2"]), W["b2"])
+    return H1, H2, logits(H2, bf16(W["W3"]), W["b3"])
+
+
+def grid_ratios16(W, X, D):
+    """:func:`grid_ratios` with H1 and H2 rounded to bf16 as the kernel stores them."""
+    u = units(D)
+    H1, H2, _ = forward16(W, X)
+    out = []
+    for A, w, b, unit in ((X, W["W1"], W["b1"], u[0]), (H1, W["W2"], W["b2"], u[0] * u[1]), (H2, W["W3"], W["b3"], u[0] * u[1] * u[2])):
+        pre = fc_pre(A, w, b)[0]
+        assert torch.equal(pre / unit, (pre / unit).round()), "a sum off its grid"
+        out.append(float(exactness(A, w, b, unit).max()) if A.shape[0] else 0.0)
+    return out
+
+
+def _isum(lo, hi, Wm):
+    """The range of ``sum_n d[r, n] Wm[n, k]`` over ``d`` in ``[lo, hi]``: each end chosen by the sign of the weight."""
+    Wp, Wn = Wm.clamp_min(0), Wm.clamp_max(0)
+    return lo @ Wp + hi @ Wn, hi @ Wp + lo @ Wn
+
+
+def _log2_lsb(t):
+    return torch.log2(lsb(t))  # +inf for zero
+
+
+def _iratio(lo, hi, Wm):
+    """``sum |term| / unit`` of every element of ``d Wm`` for ``d`` anywhere in ``[lo, hi]``: the sizes from the larger end, the unit
+    the finest bit of any term either end can give (the lowest bit of a product is the product of the lowest
+    bits). ``[rows, K]``; 0 where there is no term."""
+    mag = torch.maximum(lo.abs(), hi.abs()) @ Wm.abs()
+    ed = torch.minimum(_log2_lsb(lo), _log2_lsb(hi))
+    e = (ed[:, :, None] + _log2_lsb(Wm)[None, :, :]).amin(1)
+    unit = torch.where(torch.isfinite(e), torch.exp2(e), torch.ones_like(e))
+    return mag / unit
+
+
+def step16(W, X, y):
+    """One step of one peer as the bf16 epoch kernel takes it (section comment): the exact forward, the loss terms, the
+    predictions, ``eps_lp`` / ``eps_sm``, and for ``dlog`` ``[rows, D3]``, ``dH2`` and ``dH1`` the central value with the interval
+    ``*_lo`` / ``*_hi`` the kernel's own value lies in; ``g``: the six gradients of the central values; ``inexact``: how many
+    elements of the two dgrad sums miss the exactness condition."""
+    D3 = W["b3"].shape[0]
+    rows = X.shape[0]
+    W3, W2 = bf16(W["W3"]), bf16(W["W2"])
+    H1, H2, z = forward16(W, X)
+    loss, pred, sm = head(z, y)
+    eps_lp, eps_sm = eps_softmax(z)
+    ref = sm.clone()
+    ref[torch.arange(rows), y] -= 1.0
+    ref = ref / rows
+    e = 0.0 if D3 == 1 else eps_sm / rows
+    s = dict(X=X, y=y, rows=rows, H1=H1, H2=H2, z=z, loss=loss, pred=pred, eps_lp=eps_lp, eps_sm=eps_sm)
+    s["dlog"], s["dlog_lo"], s["dlog_hi"] = bf16(ref), bf16(ref - e), bf16(ref + e)
+    m2, m1 = H2 > 0, H1 > 0
+    lo, hi = _isum(s["dlog_lo"], s["dlog_hi"], W3)
+    s["dH2"], s["dH2_lo"], s["dH2_hi"] = bf16(m2 * (s["dlog"] @ W3)), bf16(m2 * lo), bf16(m2 * hi)
+    lo, hi = _isum(s["dH2_lo"], s["dH2_hi"], W2)
+    s["dH1"], s["dH1_lo"], s["dH1_hi"] = bf16(m1 * (s["dH2"] @ W2)), bf16(m1 * lo), bf16(m1 * hi)
+    s["inexact"] = int((_iratio(s["dlog_lo"], s["dlog_hi"], W3) >= LIM).sum()) + int((_iratio(s["dH2_lo"], s["dH2_hi"], W2) >= LIM).sum())
+    pad = torch.zeros(rows, 16, dtype=F64)
+    pad[:, :D3] = s["dlog"]
+    s["g"] = wgrads(X, H1, H2, s["dH1"], s["dH2"], pad, D3)
+    return s
+
+
+def straddle(s):
+    """The fraction of the elements of dlog, dH2 and dH1 whose interval holds more than one value."""
+    return {k: float((s[k + "_lo"] != s[k + "_hi"]).double().mean()) for k in ("dlog", "dH2", "dH1")}
+
+
+def bounds16(s, Bpad):
+    """The radius of each of the six gradients of :func:`step16`'s step (section comment, "Gradients")."""
+    out = {}
+    one = torch.ones(s["rows"], 1, dtype=F64)
+    for up, other, kw, kb in (("dlog", s["H2"], "W3", "b3"), ("dH2", s["H1"], "W2", "b2"), ("dH1", s["X"], "W1", "b1")):
+        lo, hi = s[up + "_lo"], s[up + "_hi"]
+        wid, big = hi - lo, torch.maximum(lo.abs(), hi.abs())
+        eu = torch.minimum(_log2_lsb(lo), _log2_lsb(hi)).amin(0)  # the finest bit of each column of the upstream, over the batch
+        for k, A in ((kw, other), (kb, one)):
+            mag = big.t() @ A.abs()
+            e = eu[:, None] + _log2_lsb(A).amin(0)[None, :]
+            unit = torch.where(torch.isfinite(e), torch.exp2(e), torch.ones_like(e))
+            r = wid.t() @ A.abs() + torch.where(mag / unit < LIM, torch.zeros_like(mag), gamma(Bpad) * mag)
+            out[k] = r[:, 0] if k == kb else r
+    return out
+
+
+C1, C2 = 1.0 - R.f32(BETA1), 1.0 - R.f32(BETA2)  # exact in fp32
+FLUSH32 = 2.0 ** -125
+
+
+def adam_coeffs16(hp, k):
+    """``(lr_t, inv, relative bound of lr_t, relative bound of inv)`` of ``persist::bias_corr`` at optimizer step ``k`` (from 1):
+    the values in double from the fp32 betas, the bounds of the section comment ("Bias correction")."""
+    b1, b2 = R.f32(BETA1), R.f32(BETA2)
+    r = lambda b: 2 * U * b ** k / (1.0 - b ** k) + U
+    return R.f32(hp["lr"]) / (1.0 - b1 ** k), 1.0 / math.sqrt(1.0 - b2 ** k), SECOND * (r(b1) + U), SECOND * (r(b2) / 2 + 3 * U)
+
+
+def adam_moments16(hp, w, g, dg, m, v, bm, bv):
+    """One step of the kernel's ``upd<true>`` moments from ``m``, ``v`` (known to ``bm``, ``bv``) on the gradient ``g`` (known to ``dg``), the
+    weight-decay fma included: ``(m', v', bm', bv')``."""
+    wd = R.f32(hp.get("wd", 0.0))
+    if wd != 0.0:
+        g = g + wd * w
+        dg = dg + U * g.abs()
+    b1, b2 = R.f32(BETA1), R.f32(BETA2)
+    m1 = b1 * m + C1 * g
+    bm1 = b1 * bm + U * m1.abs() + C1 * (U * g.abs() + dg)
+    v1 = b2 * v + C2 * g * g
+    top = (g.abs() + dg) ** 2
+    bv1 = b2 * bv + U * v1 + C2 * (2 * g.abs() * dg + dg * dg + 2 * U * top) + FLUSH32
+    return m1, v1, SECOND * bm1, SECOND * bv1
+
+
+def moments16(hp, w, gs, rs):
+    """The moments after the steps ``gs`` (radii ``rs``) from zero moments with the weights frozen: ``(m, v, bm, bv)``."""
+    assert R.f32(hp["lr"]) == 0.0 and hp.get("wd", 0.0) == 0.0
+    m, v, bm, bv = (torch.zeros_like(w) for _ in range(4))
+    for g, r in zip(gs, rs):
+        m, v, bm, bv = adam_moments16(hp, w, g, r, m, v, bm, bv)
+    return m, v, bm, bv
+
+
+def learn_refs16(c, p, hp):
+    """Part (d) of the bf16 file: peer ``p``'s float64 epoch with the kernel's bf16 roundings under the pinned order, and the
+    fp32 twin's: ``(ref, alt)``."""
+    out = []
+    for kw in (dict(), dict(mm=mm32_permuted(torch.Generator().manual_seed(p)), f32=True)):
+        out.append(epoch(c["W"][p], c["x"][p], c["y"][p], epoch_perm32(c["n"][p], 0, p), c["B"], hp, **kw)[0])
+    return out

@@ -422,3 +422,140 @@ def test_f32_learning_cases_are_not_chaotic(shape, hp):
         floors = {k: M.rel_update(alt[k], ref[k], c["W"][p][k]) for k in M.NAMES}
         print(f"peer {p}: " + ", ".join(f"{k} {v:.2e}" for k, v in floors.items()))
         assert 0 < max(floors.values()) < 1e-4, floors
+
+
+# ---------------------------------------------------------------------------------------------
+# the bf16 epoch kernel's oracle (tests/test_mlp_bf16_epoch_oracle_gpu.py)
+# ---------------------------------------------------------------------------------------------
+def _steps16(c, p):
+    perm = M.epoch_perm32(c["n"][p], 0, p)
+    for s in range(0, c["n"][p], c["B"]):
+        idx = torch.as_tensor(perm[s: s + c["B"]], dtype=torch.int64)
+        yield M.step16(c["W"][p], c["x"][p][idx].double(), c["y"][p][idx].long())
+
+
+@pytest.mark.parametrize("D0,D3,B,n,seed", M.bf16_grid_cases(), ids=lambda v: "-".join(map(str, v)) if isinstance(v, tuple) else str(v))
+def test_bf16_grid_cases_meet_the_oracles_conditions(D0, D3, B, n, seed):
+    """Every grid case of the bf16 file, both peers, every step of the first epoch order: the forward with H1 and H2
+    rounded to bf16 is exact (``sum |term| / unit < 2^24`` at fc1, fc2, fc3), no element of the two dgrad sums misses the
+    exactness condition whichever end of its interval each upstream element takes, and the interval oracle stays
+    sharp: every tensor's radius is at most 2^-5 of its gradient in the 2-norm, at most 5 % of dlog and at most
+    25 % of dH1 straddle. (A case over a cap gets another seed in ``BF16_SEED``; the caps stay.)"""
+    c = M.case32(D0, D3, B, M.f32_family(D3), n, seed=seed)
+    worst = dict(dlog=0.0, dH2=0.0, dH1=0.0, radius=0.0)
+    for p in range(2):
+        W = c["W"][p]
+        assert all(torch.equal(M.bf16(W[k]), W[k]) for k in ("W1", "W2", "W3")) and all(torch.equal(v.float().double(), v) for v in W.values())
+        assert max(M.grid_ratios16(W, c["x"][p].double(), c["D"])) < M.LIM
+        for s in _steps16(c, p):
+            assert s["inexact"] == 0
+            assert torch.equal(s["z"].float().double(), s["z"])
+            for k in ("dlog", "dH2", "dH1"):
+                assert ((s[k + "_lo"] <= s[k]) & (s[k] <= s[k + "_hi"])).all()
+            if D3 == 16:
+                assert torch.equal(s["z"][:, 0], s["z"][:, 1])
+            for k, v in M.straddle(s).items():
+                worst[k] = max(worst[k], v)
+            if D3 == 1:
+                assert all(not s[k].any() for k in ("dlog_lo", "dlog_hi", "dH1_lo", "dH1_hi")) and not s["loss"].any()
+                continue
+            b = M.bounds16(s, M.bpad(B))
+            for k in M.NAMES:
+                assert float(s["g"][k].norm()) > 0
+                worst["radius"] = max(worst["radius"], float(b[k].norm() / s["g"][k].norm()))
+    print(", ".join(f"{k} {v:.2e}" for k, v in worst.items()))
+    assert worst["radius"] <= 2.0 ** -5 and worst["dlog"] <= 0.05 and worst["dH1"] <= 0.25
+
+
+@pytest.mark.parametrize("D0,D3,B,rows", [(784, 10, 64, 64), (40, 16, 24, 23), (776, 16, 40, 40), (264, 10, 48, 33), (784, 10, 32, 1)])
+def test_bf16_emulated_step_stays_inside_the_intervals(D0, D3, B, rows):
+    """The kernel's step emulated with every sum in fp32 over a permuted reduction axis, the softmax in fp32 and a
+    perturbation of ``0.9 eps_sm / rows`` of either sign on every dlogits element before its rounding: H1, H2 and the
+    logits are the oracle's bit for bit, dlog, dH2 and dH1 lie in their intervals, the six gradients within
+    :func:`bounds16` of the central ones; and the radius is sharp enough to see one batch row missing."""
+    c = M.case32(D0, D3, B, M.f32_family(D3), (rows, rows))
+    for p in range(2):
+        W, X, y = c["W"][p], c["x"][p].double(), c["y"][p].long()
+        s = M.step16(W, X, y)
+        mm = M.mm32_permuted(torch.Generator().manual_seed(p))
+        H1 = M.bf16((mm(X, W["W1"].t()) + W["b1"]).float().double().clamp_min(0))
+        H2 = M.bf16((mm(H1, W["W2"].t()) + W["b2"]).float().double().clamp_min(0))
+        z = (mm(H2, W["W3"].t()) + W["b3"]).float().double()
+        assert torch.equal(H1, s["H1"]) and torch.equal(H2, s["H2"]) and torch.equal(z, s["z"])
+        sm = torch.softmax(z.float(), 1).double()
+        sm[torch.arange(rows), y] -= 1.0
+        sign = torch.randint(0, 2, sm.shape, generator=torch.Generator().manual_seed(5 + p)).double() * 2 - 1
+        dl = M.bf16(((sm + 0.9 * s["eps_sm"] * sign) / rows).float().double())
+        zero = torch.zeros((), dtype=F64)
+        dH2 = M.bf16(torch.where(H2 > 0, mm(dl, W["W3"]), zero))
+        dH1 = M.bf16(torch.where(H1 > 0, mm(dH2, W["W2"]), zero))
+        for k, t in (("dlog", dl), ("dH2", dH2), ("dH1", dH1)):
+            assert ((s[k + "_lo"] <= t) & (t <= s[k + "_hi"])).all(), k
+        assert rows == 1 or (dl != s["dlog"]).any(), "the perturbation moved nothing"
+        one = torch.ones(rows, 1, dtype=F64)
+        g = {"W1": mm(dH1.t(), X), "b1": mm(dH1.t(), one)[:, 0], "W2": mm(dH2.t(), H1), "b2": mm(dH2.t(), one)[:, 0], "W3": mm(dl.t(), H2), "b3": mm(dl.t(), one)[:, 0]}
+        bnd = M.bounds16(s, M.bpad(B))
+        for k in M.NAMES:
+            err = (g[k] - s["g"][k]).abs()
+            assert (err <= bnd[k]).all(), (k, float((err / bnd[k].clamp_min(1e-300)).max()))
+            assert float(bnd[k].norm()) < 2.0 ** -5 * float(s["g"][k].norm()) / max(1.0, rows / 32), f"{k}: a radius that says nothing"
+
+
+def test_bf16_bias_correction_bounds():
+    """``adam_coeffs16`` against ``persist::bias_corr`` emulated in fp32 (``pow`` correctly rounded, then each fp32 operation):
+    inside the bounds at k = 1 .. 40 and at 1000; the bounds tell every k from k + 1 by a factor of 100 at least."""
+    hp = dict(kind=0, lr=1e-3)
+    f = np.float32
+    b1, b2 = f(M.BETA1), f(M.BETA2)
+    for k in list(range(1, 41)) + [1000]:
+        lr_t, inv, r_lr, r_inv = M.adam_coeffs16(hp, k)
+        e_lr = f(hp["lr"]) / (f(1) - f(float(b1) ** k))
+        e_inv = f(1) / np.sqrt(f(1) - f(float(b2) ** k), dtype=f)
+        assert abs(float(e_lr) - lr_t) <= r_lr * lr_t and abs(float(e_inv) - inv) <= r_inv * inv, k
+        nxt = M.adam_coeffs16(hp, k + 1)
+        if k <= 40:
+            assert abs(nxt[0] - lr_t) > 100 * r_lr * lr_t and abs(nxt[1] - inv) > 100 * r_inv * inv, k
+    assert 1.1e-4 < 2 * M.adam_coeffs16(hp, 1)[3] < 1.3e-4
+
+
+def test_bf16_moments_emulation_stays_inside_its_bounds():
+    """Five steps of the kernel's ``upd<true>`` moment recursions emulated in fp32 on gradients moved by up to their radius,
+    some radii as large as the element: within :func:`moments16`; one step with weight decay within :func:`adam_moments16`."""
+    g = torch.Generator().manual_seed(13)
+    n = 4096
+    w = _r(torch.randn(n, generator=g) * 0.1)
+    gs = [_r(torch.randn(n, generator=g) * torch.exp2(torch.randint(-20, 0, (n,), generator=g).float())) for _ in range(5)]
+    rs = [x.abs() * torch.exp2(torch.randint(-12, 1, (n,), generator=g).float()).double() * (torch.rand(n, generator=g) < 0.3) for x in gs]
+    b1, b2 = M.R.f32(M.BETA1), M.R.f32(M.BETA2)
+    for wd in (0.0, 1e-4):
+        hp = dict(kind=0, lr=0.0 if wd == 0.0 else 1e-3, wd=wd)
+        me, ve = torch.zeros(n, dtype=F64), torch.zeros(n, dtype=F64)
+        steps = 5 if wd == 0.0 else 1
+        for x, r in zip(gs[:steps], rs[:steps]):
+            gk = _r(x + r * (torch.rand(n, generator=g).double() * 2 - 1))
+            gk = torch.where((gk - x).abs() <= r, gk, x)
+            gk = _fma(torch.full_like(w, M.R.f32(wd)), w, gk)
+            me = _fma(torch.full_like(w, b1), me, _r(M.C1 * gk))
+            ve = _fma(torch.full_like(w, b2), ve, _r(M.C2 * _r(gk * gk)))
+        if wd == 0.0:
+            m, v, bm, bv = M.moments16(hp, w, gs, rs)
+        else:
+            zero = torch.zeros_like(w)
+            m, v, bm, bv = M.adam_moments16(hp, w, gs[0], rs[0], zero, zero, zero, zero)
+        assert ((me - m).abs() <= bm).all() and ((ve - v).abs() <= bv).all()
+        if wd:  # where the radius is zero the bound is a few ulps: it sees the weight-decay term
+            assert float((bm / m.abs().clamp_min(1e-300))[rs[0] == 0].median()) < 2.0 ** -20
+
+
+@pytest.mark.parametrize("hp", list(M.BF16_LEARN_HP))
+@pytest.mark.parametrize("shape", M.BF16_LEARN_SHAPES, ids=lambda s: "-".join(map(str, s)))
+def test_bf16_learning_cases_are_not_chaotic(shape, hp):
+    """Part (d)'s cases of the bf16 file: 8 times the twin's floor is at most 1e-2 for every tensor of both peers (a
+    stale weight or a step applied twice moves a tensor by the order of 1 / steps)."""
+    D0, D3, B = shape
+    c = M.case32(D0, D3, B, "randn16", M.BF16_LEARN[B], seed=M.BF16_LEARN_SEED.get(shape, 0))
+    for p in range(2):
+        ref, alt = M.learn_refs16(c, p, M.BF16_LEARN_HP[hp])
+        floors = {k: M.rel_update(alt[k], ref[k], c["W"][p][k]) for k in M.NAMES}
+        print(f"peer {p}: " + ", ".join(f"{k} {v:.2e}" for k, v in floors.items()))
+        assert 0 < 8 * max(floors.values()) <= 1e-2, floors
