@@ -290,56 +290,69 @@ void fl_neighbor_mix(float* stacked, int P, int64_t n, int64_t ld, const MixPlan
   }
 }
 
-// per-coordinate median of K ≤ 16 models: branch-free compare-exchange network over K registers,
-// the result stored into P destination rows (every peer that takes the aggregate). Row pointers
-// travel as kernel arguments (no pointer table on the device, no H2D copy); each thread loads its
-// coordinate from every row before storing, so destinations may alias sources.
+// The per-coordinate sorts below order their values as
+//   −inf < … < −0.0 < +0.0 < … < +inf < NaN:
+// a NaN (a peer that sent one) is the largest value, as in numpy's and torch's sort, never a vote for
+// its neighbour (fminf / fmaxf would drop it and duplicate the other operand). The network runs on a
+// monotone integer key of the float's bits (a negative float's magnitude bits inverted; every NaN
+// the quiet 0x7fc00000, above +inf) with integer min / max, and maps back: a non-NaN value comes
+// out bit for bit.
+__device__ __forceinline__ int sort_key(float v) {
+  const int b = v != v ? 0x7fc00000 : __float_as_int(v);
+  return b ^ ((b >> 31) & 0x7fffffff);
+}
+__device__ __forceinline__ float sort_value(int key) { return __int_as_float(key ^ ((key >> 31) & 0x7fffffff)); }
+
+// branch-free compare-exchange network over K registers: v ascending
+template <int K>
+__device__ __forceinline__ void sort_keys(int (&v)[K]) {
+#pragma unroll
+  for (int a = 0; a < K; ++a) {
+#pragma unroll
+    for (int b = 0; b < K - 1 - a; ++b) {
+      const int lo = min(v[b], v[b + 1]);
+      v[b + 1] = max(v[b], v[b + 1]);
+      v[b] = lo;
+    }
+  }
+}
+
+// per-coordinate median of K ≤ 16 models: the network above over K registers, the result stored
+// into P destination rows (every peer that takes the aggregate). Row pointers travel as kernel
+// arguments (no pointer table on the device, no H2D copy); each thread loads its coordinate from
+// every row before storing, so destinations may alias sources. A NaN among the middle values makes
+// the output NaN.
 template <int K>
 __global__ __launch_bounds__(FL_BLOCK) void k_coordinate_median(OutPtrs outs, int P, RowPtrs rows, int64_t n) {
   const int64_t stride = (int64_t)gridDim.x * FL_BLOCK;
   for (int64_t i = blockIdx.x * FL_BLOCK + threadIdx.x; i < n; i += stride) {
-    float v[K];
+    int v[K];
 #pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = rows.p[k][i];
-#pragma unroll
-    for (int a = 0; a < K; ++a) {
-#pragma unroll
-      for (int b = 0; b < K - 1 - a; ++b) {
-        const float lo = fminf(v[b], v[b + 1]);
-        v[b + 1] = fmaxf(v[b], v[b + 1]);
-        v[b] = lo;
-      }
-    }
-    const float med = (K & 1) ? v[(K - 1) / 2] : 0.5f * (v[K / 2 - 1] + v[K / 2]);
+    for (int k = 0; k < K; ++k) v[k] = sort_key(rows.p[k][i]);
+    sort_keys<K>(v);
+    const float med = (K & 1) ? sort_value(v[(K - 1) / 2]) : 0.5f * (sort_value(v[K / 2 - 1]) + sort_value(v[K / 2]));
     for (int p = 0; p < P; ++p) outs.p[p][i] = med;
   }
 }
 
 // per-coordinate trimmed mean of K ≤ 16 models: the median's compare-exchange network, then the
 // kept values v[t .. K-t) summed in ascending order in fp32 and divided by K-2t (0 ≤ 2t < K, a
-// run-time argument). Loads every row's coordinate before any store: destinations may alias sources.
+// run-time argument); a NaN among the kept values makes the output NaN. Loads every row's coordinate
+// before any store: destinations may alias sources.
 template <int K>
 __global__ __launch_bounds__(FL_BLOCK) void k_trimmed_mean(OutPtrs outs, int P, RowPtrs rows, int t, int64_t n) {
   const int64_t stride = (int64_t)gridDim.x * FL_BLOCK;
   const float cnt = (float)(K - 2 * t);
   for (int64_t i = blockIdx.x * FL_BLOCK + threadIdx.x; i < n; i += stride) {
-    float v[K];
+    int v[K];
 #pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = rows.p[k][i];
-#pragma unroll
-    for (int a = 0; a < K; ++a) {
-#pragma unroll
-      for (int b = 0; b < K - 1 - a; ++b) {
-        const float lo = fminf(v[b], v[b + 1]);
-        v[b + 1] = fmaxf(v[b], v[b + 1]);
-        v[b] = lo;
-      }
-    }
+    for (int k = 0; k < K; ++k) v[k] = sort_key(rows.p[k][i]);
+    sort_keys<K>(v);
     float s = 0.f;
     // static register indices (a dynamic v[t + k] would put v in scratch)
 #pragma unroll
     for (int k = 0; k < K; ++k)
-      if (k >= t && k < K - t) s += v[k];
+      if (k >= t && k < K - t) s += sort_value(v[k]);
     const float mean = s / cnt;
     for (int p = 0; p < P; ++p) outs.p[p][i] = mean;
   }

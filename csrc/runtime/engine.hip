@@ -1000,8 +1000,8 @@ int myfyp_coordinate_median(float* out, const uint64_t* srcs, int K, int64_t n, 
 }
 int myfyp_trimmed_mean_multi(const uint64_t* outs, int P, const uint64_t* srcs, int K, int trim, int64_t n, void* stream) {
   if (!rows_ok(K, "trimmed_mean") || !rows_ok(P, "trimmed_mean outputs")) return 2;
-  if (trim < 0 || 2 * trim >= K) {
-    g_last_error = "trimmed_mean: 0 <= 2*trim < K";
+  if (n < 1 || trim < 0 || 2 * trim >= K) {
+    g_last_error = "trimmed_mean: n >= 1 and 0 <= 2*trim < K";
     return 2;
   }
   RowPtrs rows{};

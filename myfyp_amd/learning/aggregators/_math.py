@@ -37,7 +37,8 @@ def weighted_mean(param_lists: Sequence[Sequence], weights: Sequence[float]) -> 
 
 
 def coordinate_median(param_lists: Sequence[Sequence]) -> List:
-    """Per-coordinate median across models (even count → mean of the two middle values)."""
+    """Per-coordinate median across models (even count → mean of the two middle values). A NaN sorts
+    last, above +inf: the median is NaN only when a NaN reaches the middle."""
     first = param_lists[0][0]
     if _is_torch(first):
         from myfyp_amd import ops
@@ -45,8 +46,13 @@ def coordinate_median(param_lists: Sequence[Sequence]) -> List:
         return ops.coordinate_median([list(p) for p in param_lists])
     out = []
     for layer_idx in range(len(param_lists[0])):
-        stacked = np.stack([np.asarray(p[layer_idx]) for p in param_lists])
-        out.append(np.median(stacked, axis=0).astype(stacked.dtype))
+        # sort and pick the middle, as the torch branch and the kernel do (np.median would turn any
+        # NaN of a coordinate into a NaN median)
+        s = np.sort(np.stack([np.asarray(p[layer_idx]) for p in param_lists]), axis=0)
+        k = len(s)
+        with np.errstate(invalid="ignore"):
+            med = s[(k - 1) // 2] if k % 2 else 0.5 * (s[k // 2 - 1] + s[k // 2])
+        out.append(med.astype(s.dtype))
     return out
 
 

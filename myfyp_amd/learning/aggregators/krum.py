@@ -12,6 +12,10 @@ from myfyp_amd.learning.aggregators.aggregator import Aggregator, NoModelsToAggr
 from myfyp_amd.learning.frameworks.p2pfl_model import P2PFLModel
 
 
+def _nan_last(v: float) -> float:
+    return float("inf") if v != v else float(v)
+
+
 class Krum(Aggregator):
     """Score each model by the summed squared distance to its ``n - f - 2`` nearest peers; average
     the ``m`` best (m=1 → classic Krum)."""
@@ -38,14 +42,22 @@ class Krum(Aggregator):
             # distances (from differences) and scores on the rows' device; only K scores reach the host
             _, score, _ = ops.krum_into([f_.contiguous() for f_ in flats], [], [float(m.get_num_samples()) for m in models], self.f, self.m)
             scores = score.cpu().numpy()
-            order = np.argsort(scores, kind="stable")
         else:
+            # as ops.krum_into: distances from differences (a row of ±inf is at +inf or NaN of the
+            # others, never at a cancelled finite value), a NaN ordering as +inf
             X = np.stack(flats)
-            sq = (X * X).sum(1)
-            d = np.maximum(sq[:, None] + sq[None, :] - 2 * X @ X.T, 0)
-            k = max(1, n - self.f - 2)
-            scores = [np.sort(np.delete(d[i], i))[:k].sum() for i in range(n)]
-            order = np.argsort(scores)
+            d = np.zeros((n, n))
+            with np.errstate(invalid="ignore", over="ignore"):
+                for i in range(n):
+                    for j in range(i + 1, n):
+                        d[i, j] = d[j, i] = np.square(X[i] - X[j]).sum()
+                k = min(max(1, n - self.f - 2), n - 1)
+                scores = []
+                for i in range(n):
+                    near = sorted((j for j in range(n) if j != i), key=lambda j: (_nan_last(d[i, j]), j))[:k]
+                    scores.append(float(sum(d[i, j] for j in near)))
+        # the lower index wins a tie, a NaN score orders last (with +inf)
+        order = sorted(range(n), key=lambda i: (_nan_last(scores[i]), i))
         chosen = [models[i] for i in order[: max(1, min(self.m, n))]]
         params = weighted_mean([m.get_parameters() for m in chosen], [m.get_num_samples() for m in chosen])
         contributors: List[str] = []

@@ -177,7 +177,11 @@ def _host_ptrs(ts: Sequence[torch.Tensor]) -> ctypes.c_void_p:
 
 def median_into(rows: Sequence[torch.Tensor], outs: Sequence[torch.Tensor]) -> None:
     """``outs[p] = coordinate-wise median(rows)`` for 1-D fp32 rows; on the GPU one launch
-    (``k_coordinate_median<K>``) for K <= 16 rows and <= 16 outputs, which may alias the rows."""
+    (``k_coordinate_median<K>``) for K <= 16 rows and <= 16 outputs, which may alias the rows.
+
+    On every device a coordinate is sorted in the order ``-inf < ... < -0.0 < +0.0 < ... < +inf < NaN``:
+    a NaN is the largest value, so the median is NaN only when a NaN reaches the middle (more than
+    ``(K - 1) // 2`` of them in one coordinate), and the even-K median is ``0.5 * (a + b)``."""
     k = len(rows)
     if rows[0].device.type == "cuda" and k <= 16 and len(outs) <= 16 and all(t.is_contiguous() and t.dtype == torch.float32 for t in [*rows, *outs]):
         src, keep_s = _host_ptrs(rows)
@@ -199,13 +203,17 @@ def _native_rows(rows: Sequence[torch.Tensor], outs: Sequence[torch.Tensor]) -> 
 def trimmed_mean_into(rows: Sequence[torch.Tensor], outs: Sequence[torch.Tensor], trim: int) -> None:
     """``outs[p] = mean(sorted(rows)[trim : K - trim])`` per coordinate for 1-D fp32 rows
     (``0 <= 2·trim < K``); on the GPU one launch (``k_trimmed_mean<K>``) for K <= 16 rows and
-    <= 16 outputs, which may alias the rows. Elsewhere: sort and mean in float64 (the oracle)."""
+    <= 16 outputs, which may alias the rows. Elsewhere: sort and mean in float64.
+
+    On every device a coordinate is sorted in the order ``-inf < ... < -0.0 < +0.0 < ... < +inf < NaN``:
+    a NaN is the largest value and is trimmed first; with more than ``trim`` of them in one
+    coordinate a NaN is kept and that output is NaN."""
     k = len(rows)
     trim = int(trim)
     if trim < 0 or 2 * trim >= k:
         raise ValueError(f"trimmed mean of {k} rows cannot drop {trim} from each end")
     if _native_rows(rows, outs):
-        if not outs:
+        if not outs or rows[0].numel() == 0:
             return
         src, keep_s = _host_ptrs(rows)
         dst, keep_d = _host_ptrs(outs)
