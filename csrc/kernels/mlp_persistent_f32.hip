@@ -63,6 +63,8 @@
 //   starts with the whole forward of H1(t) (K loop, reduction, publish) after the barrier that ends
 //   C2 of step t − 1. Both orders add the same terms in the same order: H1 is bit-identical.
 #include <atomic>
+#include <climits>
+#include <vector>
 
 #include "mlp_persistent.h"
 #include "persist_common.h"
@@ -2345,104 +2347,71 @@ size_t persistent_f32_lds_ks(const MLPArgs& a, int KS, bool rh = false) {
   return lo > lh ? lo : lh;
 }
 
-bool v3_supported(const MLPArgs& a) {
+// the shapes layout 1 (rh false) and layout 3 (rh true) are built for
+bool f32_shape_ok(const MLPArgs& a, bool rh) {
   if (a.D1 != PD1 || a.D2 != PD2 || a.D3 < 1 || a.D3 > 16) return false;
   if (a.D0 % 8 != 0 || ks1_of(a.D0) > KS1_MAX) return false;
   if (a.Bpad != 32 && a.Bpad != 64) return false;
   if ((a.cg == nullptr) != (a.cl == nullptr)) return false;
-  if (a.cg != nullptr && a.anchor != nullptr) return false;
-  return persistent_f32_lds_ks(a, 1, true) <= 160 * 1024;
+  if (a.cg != nullptr && a.anchor != nullptr) return false;  // one extra term per element (mlp_f32_common.h)
+  return persistent_f32_lds_ks(a, 1, rh) <= 160 * 1024;
 }
+bool v3_supported(const MLPArgs& a) { return f32_shape_ok(a, true); }
 
-template <int BP, bool ADAM, bool EXTRA, int KS, bool RH = false, bool FUSE = false, int K24 = 0, int FRAG = 0, int D0C = 0>
-const void* f32_fn() {
-  return (const void*)mlp_persistent_f32_epoch<BP, ADAM, EXTRA, KS, RH, FUSE, K24, FRAG, D0C>;
-}
 // the input width the static-D0 kernels are built for (MNIST: 28 x 28)
 constexpr int STATIC_D0 = 784;
 // the fused forward (owner32's FUSE) is instantiated for layout 1 at K split 1 without an extra term
 __host__ __device__ constexpr bool fuse_inst(int KS, bool RH) { return KS == 1 && !RH; }
-template <int BP, int KS, bool RH = false>
-hipError_t prepare_f32_bp(int lds) {
-  const void* fns[4] = {f32_fn<BP, true, false, KS, RH>(), f32_fn<BP, true, true, KS, RH>(), f32_fn<BP, false, false, KS, RH>(),
-                        f32_fn<BP, false, true, KS, RH>()};
-  for (const void* fn : fns) {
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return e;
-  }
-  if constexpr (fuse_inst(KS, RH)) {
-    // (the last argument: the H1 fragment image, launch_f32_bp)
-    for (const void* fn : {f32_fn<BP, true, false, KS, RH, true>(), f32_fn<BP, false, false, KS, RH, true>(),
-                           f32_fn<BP, true, false, KS, RH, true, 1>(), f32_fn<BP, false, false, KS, RH, true, 1>(),
-                           f32_fn<BP, true, false, KS, RH, true, 0, 1>(), f32_fn<BP, false, false, KS, RH, true, 0, 1>(),
-                           f32_fn<BP, true, false, KS, RH, true, 1, 1>(), f32_fn<BP, false, false, KS, RH, true, 1, 1>()}) {
-      const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      if (e != hipSuccess) return e;
-    }
-    // the MNIST width as a constant (owner32's D0C, MYFYP_F32_STATIC_D0): the K24 fragment kernels only
-    if constexpr (KS == 1) {
-      for (const void* fn : {f32_fn<BP, true, false, 1, RH, true, 1, 1, STATIC_D0>(), f32_fn<BP, false, false, 1, RH, true, 1, 1, STATIC_D0>()}) {
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return e;
-      }
-    }
-  }
-  return hipSuccess;
+
+// The instantiations of mlp_persistent_f32_epoch, each with its template arguments. f32_rows() is the only
+// place that names them: preparation, the occupancy query and the launch take fn from a row of it.
+struct F32Row {
+  int BP, KS, K24, FRAG, D0C;
+  bool ADAM, EXTRA, RH, FUSE;
+  const void* fn;
+};
+template <int BP, bool ADAM, bool EXTRA, int KS, bool RH, bool FUSE = false, int K24 = 0, int FRAG = 0, int D0C = 0>
+void f32_add(std::vector<F32Row>& t) {
+  t.push_back({BP, KS, K24, FRAG, D0C, ADAM, EXTRA, RH, FUSE, (const void*)mlp_persistent_f32_epoch<BP, ADAM, EXTRA, KS, RH, FUSE, K24, FRAG, D0C>});
 }
-template <int BP, int KS, bool RH = false>
-void launch_f32_bp(const MLPArgs& a, const MLPPersistF32Bufs& pb, hipStream_t s, int p_base, size_t lds, int attempt, bool fuse, bool h1_frag,
-                   bool static_d0) {
-  const dim3 grid(grid_of(KS, RH, RH ? roles3_of(KS, BP) : roles_of(KS))), block(NT);
-  const bool adam = a.opt.kind == 0;
-  const bool extra = a.anchor != nullptr || a.cg != nullptr;
+// one (batch tile, K split, layout): optimizer x extra term, and where the fused forward is instantiated its
+// kernels: no extra term, K24 and FRAG only among them, the static width only at K split 1 with K24 = FRAG = 1
+template <int BP, int KS, bool RH = false, bool ADAM = true>
+void f32_add_rows(std::vector<F32Row>& t) {
+  f32_add<BP, ADAM, false, KS, RH>(t), f32_add<BP, ADAM, true, KS, RH>(t);
   if constexpr (fuse_inst(KS, RH)) {
-    if (fuse && !extra && h1_frag) {  // H1 and dH2 as fragment images (set by the launch where it applies)
-      if constexpr (KS == 1) {
-        if (pb.k24 == 1 && static_d0) {  // a.D0 == STATIC_D0 (set by the launch where it applies)
-          if (adam) hipLaunchKernelGGL((mlp_persistent_f32_epoch<BP, true, false, 1, RH, true, 1, 1, STATIC_D0>), grid, block, lds, s, a, pb, p_base, attempt);
-          else hipLaunchKernelGGL((mlp_persistent_f32_epoch<BP, false, false, 1, RH, true, 1, 1, STATIC_D0>), grid, block, lds, s, a, pb, p_base, attempt);
-          return;
-        }
-      }
-      if (pb.k24 == 1) {
-        if (adam) hipLaunchKernelGGL((mlp_persistent_f32_epoch<BP, true, false, KS, RH, true, 1, 1>), grid, block, lds, s, a, pb, p_base, attempt);
-        else hipLaunchKernelGGL((mlp_persistent_f32_epoch<BP, false, false, KS, RH, true, 1, 1>), grid, block, lds, s, a, pb, p_base, attempt);
-      } else {
-        if (adam) hipLaunchKernelGGL((mlp_persistent_f32_epoch<BP, true, false, KS, RH, true, 0, 1>), grid, block, lds, s, a, pb, p_base, attempt);
-        else hipLaunchKernelGGL((mlp_persistent_f32_epoch<BP, false, false, KS, RH, true, 0, 1>), grid, block, lds, s, a, pb, p_base, attempt);
-      }
-      return;
-    }
-    if (fuse && !extra && pb.k24 == 1) {  // K step 24 register-resident (set by the launch where it applies)
-      if (adam) hipLaunchKernelGGL((mlp_persistent_f32_epoch<BP, true, false, KS, RH, true, 1>), grid, block, lds, s, a, pb, p_base, attempt);
-      else hipLaunchKernelGGL((mlp_persistent_f32_epoch<BP, false, false, KS, RH, true, 1>), grid, block, lds, s, a, pb, p_base, attempt);
-      return;
-    }
-    if (fuse && !extra) {
-      if (adam) hipLaunchKernelGGL((mlp_persistent_f32_epoch<BP, true, false, KS, RH, true>), grid, block, lds, s, a, pb, p_base, attempt);
-      else hipLaunchKernelGGL((mlp_persistent_f32_epoch<BP, false, false, KS, RH, true>), grid, block, lds, s, a, pb, p_base, attempt);
-      return;
-    }
+    f32_add<BP, ADAM, false, KS, RH, true, 0, 0>(t), f32_add<BP, ADAM, false, KS, RH, true, 1, 0>(t);
+    f32_add<BP, ADAM, false, KS, RH, true, 0, 1>(t), f32_add<BP, ADAM, false, KS, RH, true, 1, 1>(t);
+    if constexpr (KS == 1) f32_add<BP, ADAM, false, KS, RH, true, 1, 1, STATIC_D0>(t);
   }
-  if (adam && !extra) hipLaunchKernelGGL((mlp_persistent_f32_epoch<BP, true, false, KS, RH>), grid, block, lds, s, a, pb, p_base, attempt);
-  else if (adam) hipLaunchKernelGGL((mlp_persistent_f32_epoch<BP, true, true, KS, RH>), grid, block, lds, s, a, pb, p_base, attempt);
-  else if (!extra) hipLaunchKernelGGL((mlp_persistent_f32_epoch<BP, false, false, KS, RH>), grid, block, lds, s, a, pb, p_base, attempt);
-  else hipLaunchKernelGGL((mlp_persistent_f32_epoch<BP, false, true, KS, RH>), grid, block, lds, s, a, pb, p_base, attempt);
+  if constexpr (ADAM) f32_add_rows<BP, KS, RH, false>(t);
+}
+const std::vector<F32Row>& f32_rows() {
+  static const std::vector<F32Row> rows = [] {
+    std::vector<F32Row> t;
+    f32_add_rows<32, 1>(t), f32_add_rows<64, 1>(t), f32_add_rows<32, 2>(t), f32_add_rows<64, 2>(t);
+    f32_add_rows<64, 4>(t), f32_add_rows<64, 8>(t);  // K splits 4 / 8: the 64-row batch tile and layout 1 only
+    // layout 3 (row heads): K split <= 2
+    f32_add_rows<32, 1, true>(t), f32_add_rows<64, 1, true>(t), f32_add_rows<32, 2, true>(t), f32_add_rows<64, 2, true>(t);
+    return t;
+  }();
+  return rows;
+}
+int bp_of(const MLPArgs& a) { return a.Bpad == 64 ? 64 : 32; }  // the batch tile a launch's kernels are instantiated for
+// the row with these template arguments, or null (not instantiated)
+const F32Row* f32_find(int BP, bool adam, bool extra, int KS, bool rh, bool fuse = false, int k24 = 0, int frag = 0, int d0c = 0) {
+  for (const F32Row& r : f32_rows())
+    if (r.BP == BP && r.ADAM == adam && r.EXTRA == extra && r.KS == KS && r.RH == rh && r.FUSE == fuse && r.K24 == k24 && r.FRAG == frag && r.D0C == d0c)
+      return &r;
+  return nullptr;
 }
 
 // Workgroups one launch of K split KS can have resident at once (occupancy calculator for the
 // instantiation: registers, LDS, 512 threads).
 int resident_capacity_ks(const MLPArgs& a, int num_cus, int KS, bool rh = false) {
   int per_cu = 0;
-  const size_t lds = persistent_f32_lds_ks(a, KS, rh);
-  const bool b64 = a.Bpad == 64;
-  const void* fn = rh ? (KS == 2 ? (b64 ? f32_fn<64, true, false, 2, true>() : f32_fn<32, true, false, 2, true>())
-                                 : (b64 ? f32_fn<64, true, false, 1, true>() : f32_fn<32, true, false, 1, true>()))
-                      : (KS == 8 ? f32_fn<64, true, false, 8>()
-                         : KS == 4 ? f32_fn<64, true, false, 4>()
-                         : KS == 2 ? (b64 ? f32_fn<64, true, false, 2>() : f32_fn<32, true, false, 2>())
-                                   : (b64 ? f32_fn<64, true, false, 1>() : f32_fn<32, true, false, 1>()));
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, NT, lds) != hipSuccess) return 0;
+  const F32Row* row = f32_find(bp_of(a), true, false, KS, rh);
+  if (row == nullptr || hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, row->fn, NT, persistent_f32_lds_ks(a, KS, rh)) != hipSuccess) return 0;
   return per_cu * num_cus;
 }
 int roles_for(const MLPArgs& a, int KS) { return f32_variant(a) == 3 ? roles3_of(KS, a.Bpad) : roles_of(KS); }
@@ -2482,13 +2451,7 @@ size_t persistent_f32_lds(const MLPArgs& a) {
 }
 
 bool mlp_persistent_f32_supported(const MLPArgs& a) {
-  if (f32_variant(a) != 1) return true;  // (layout 2 / 3's own shape checks passed in f32_variant)
-  if (a.D1 != PD1 || a.D2 != PD2 || a.D3 < 1 || a.D3 > 16) return false;
-  if (a.D0 % 8 != 0 || ks1_of(a.D0) > KS1_MAX) return false;
-  if (a.Bpad != 32 && a.Bpad != 64) return false;
-  if ((a.cg == nullptr) != (a.cl == nullptr)) return false;
-  if (a.cg != nullptr && a.anchor != nullptr) return false;  // one extra term per element (mlp_f32_common.h)
-  return persistent_f32_lds_ks(a, 1) <= 160 * 1024;
+  return f32_variant(a) != 1 || f32_shape_ok(a, false);  // (layout 2 / 3's own shape checks passed in f32_variant)
 }
 
 size_t mlp_persistent_f32_h1x_floats(int P, int Bpad) { return (size_t)P * KSLAB * 2 * Bpad * PD1; }
@@ -2523,23 +2486,11 @@ void mlp_persistent_f32_flag_layout(int* line, int* lines_per_peer, int* full_li
 
 hipError_t mlp_persistent_f32_prepare(const MLPArgs& a) {
   hipError_t e;
-  for (int KS = 1; KS <= KSMAX; KS *= 2) {
-    const int lds = (int)persistent_f32_lds_ks(a, KS);
-    if (KS > 2) {
-      if (a.Bpad != 64) continue;
-      e = KS == 4 ? prepare_f32_bp<64, 4>(lds) : prepare_f32_bp<64, 8>(lds);
-      if (e != hipSuccess) return e;
-      continue;
-    }
-    e = KS == 1 ? (a.Bpad == 64 ? prepare_f32_bp<64, 1>(lds) : prepare_f32_bp<32, 1>(lds))
-                : (a.Bpad == 64 ? prepare_f32_bp<64, 2>(lds) : prepare_f32_bp<32, 2>(lds));
+  const bool v3 = v3_supported(a);
+  for (const F32Row& r : f32_rows()) {
+    if (r.BP != bp_of(a) || (r.RH && !v3)) continue;
+    e = hipFuncSetAttribute(r.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)persistent_f32_lds_ks(a, r.KS, r.RH));
     if (e != hipSuccess) return e;
-    if (v3_supported(a)) {
-      const int l3 = (int)persistent_f32_lds_ks(a, KS, true);
-      e = KS == 1 ? (a.Bpad == 64 ? prepare_f32_bp<64, 1, true>(l3) : prepare_f32_bp<32, 1, true>(l3))
-                  : (a.Bpad == 64 ? prepare_f32_bp<64, 2, true>(l3) : prepare_f32_bp<32, 2, true>(l3));
-      if (e != hipSuccess) return e;
-    }
   }
   if (mlp_f32v2_supported(a)) {
     e = mlp_f32v2_prepare(a);
@@ -2548,177 +2499,136 @@ hipError_t mlp_persistent_f32_prepare(const MLPArgs& a) {
   return hipFuncSetAttribute((const void*)mlp_eval_f32, hipFuncAttributeMaxDynamicSharedMemorySize, (int)eval_lds32(a.D0));
 }
 
-// MYFYP_F32_PLAIN_PUB: 1 (default) payloads and flags plain for single-XCD gangs, 2 payloads only,
-// 0 everything written through (A/B); mlp_set_plain_pub overrides it (tests)
-static std::atomic<int> g_plain_override{-1};
-int mlp_plain_pub_mode() {
-  const int o = g_plain_override.load(std::memory_order_relaxed);
-  if (o >= 0) return o;
-  static const int v = [] {
-    const char* e = getenv("MYFYP_F32_PLAIN_PUB");
-    return e != nullptr ? atoi(e) : 1;
-  }();
-  return v;
-}
-extern "C" int mlp_set_plain_pub(int mode) { return g_plain_override.exchange(mode < 0 ? -1 : mode); }
+// The A/B switches of the epoch launch: MYFYP_F32_<NAME> in the environment (read once per process, default
+// 1), overridden by mlp_set_*(mode) (tests; -1: back to the environment; returns the previous override).
+// PLAIN_PUB's value is used as it is, the others are on when > 0, and both sides of those give the same bits.
+// mlp_f32_*_last(): what the last epoch launch took (-1: none yet).
+struct F32Switch {
+  const char* env;
+  std::atomic<int> forced{-1}, cached{INT_MIN}, last{-1};  // the override, the environment's value once read, the last launch
+  int mode() {
+    const int o = forced.load(std::memory_order_relaxed);
+    if (o >= 0) return o;
+    int v = cached.load(std::memory_order_relaxed);
+    if (v == INT_MIN) {
+      const char* e = getenv(env);
+      cached.store(v = e != nullptr ? atoi(e) : 1, std::memory_order_relaxed);
+    }
+    return v;
+  }
+  int set(int m) { return forced.exchange(m < 0 ? -1 : m); }
+  void report(int v) { last.store(v, std::memory_order_relaxed); }
+};
+enum { SW_PLAIN_PUB, SW_FWD_FUSE, SW_C2_STRAIGHT, SW_K24, SW_DH2_FRAG, SW_H1_FRAG, SW_STATIC_D0, SW_COUNT };
+static F32Switch g_sw[SW_COUNT] = {
+    // 1 payloads and flags plain for single-XCD gangs, 2 payloads only, 0 everything written through. No
+    // "last": what each gang decided is read with mlp_debug_plain_seen.
+    {"MYFYP_F32_PLAIN_PUB"},
+    // the owners accumulate the next step's forward inside C2 where that loop is instantiated (layout 1, K
+    // split 1, no extra term); off: the separate forward. Last: the launched layout-1/3 kernel's FUSE.
+    {"MYFYP_F32_FWD_FUSE"},
+    // the owners of layout 1 at K split 1 run C2's straight-line body in every wave whose register-resident K
+    // steps all exist; off: the guarded body everywhere. It reaches the kernel as pb.c2_straight. Last: what a
+    // layout-1 launch could take: 1 if the switch was on and D0 gives every wave its K steps (K split 1, 24 K
+    // steps or more: D0 >= 736), else 0.
+    {"MYFYP_F32_C2_STRAIGHT"},
+    // the wave that owns K step 24 (wave 0 of an owner, D0 >= 768) keeps that K step's weights and moments in
+    // registers over the step loop and runs it inside C2's straight block; off: it stays LDS-resident in its
+    // guarded form. It needs the fused forward and the straight body. Where it applies the launch takes a K24
+    // instantiation and sets pb.k24 from it (the mode as a kernel argument alone spilled: owner32). Last: the
+    // launched layout-1/3 kernel's K24.
+    {"MYFYP_F32_K24"},
+    // the heads of layout 1 publish dH2 as the owners' MFMA A fragments (dh2f[parity][hd][mt][lane], one
+    // 16-byte store per lane) and the owners' C1 loads them straight into registers; off: the [b][128] tile
+    // staged through LDS. Heads and owners read it from the same launch argument, pb.dh2_frag. Last: the
+    // launched pb.dh2_frag: 0 for layouts 2 and 3.
+    {"MYFYP_F32_DH2_FRAG"},
+    // the owners of layout 1 publish H1 as the heads' MFMA fragments (h1f[parity][g][mt][lane], one 16-byte
+    // store per lane), the heads load them straight into registers and accumulate H2 and dH2 transposed; off:
+    // the [b][256] image staged through LDS and the row-major accumulators. A template argument (head32's
+    // FRAG), not a launch argument: taken only where the fused layout-1 K-split-1 kernels are launched and dH2
+    // goes as fragments too. Last: the launched kernel's FRAG: 0 for layouts 2 and 3, K splits > 1, extra-term
+    // epochs, the separate forward and with either switch off.
+    {"MYFYP_F32_H1_FRAG"},
+    // an epoch of input width 784 (MNIST) that takes the K24 fragment kernels runs the instantiation with that
+    // width as a compile-time constant (owner32's D0C: strides as immediates, no column tests below K step 24,
+    // no multiplies); off, and at every other width: the run-time-width kernel. Last: the launched kernel has
+    // a D0C (0 for layout 2).
+    {"MYFYP_F32_STATIC_D0"},
+};
+int mlp_plain_pub_mode() { return g_sw[SW_PLAIN_PUB].mode(); }
+extern "C" int mlp_set_plain_pub(int mode) { return g_sw[SW_PLAIN_PUB].set(mode); }
 extern "C" int mlp_debug_plain_seen(int* out) {
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_plain_seen), sizeof(g_plain_seen)) == hipSuccess ? 0 : 1;
 }
+#define F32_SWITCH_API(name, sw)                                             \
+  extern "C" int mlp_set_f32_##name(int mode) { return g_sw[sw].set(mode); } \
+  extern "C" int mlp_f32_##name##_last() { return g_sw[sw].last.load(std::memory_order_relaxed); }
+F32_SWITCH_API(fwd_fuse, SW_FWD_FUSE)
+F32_SWITCH_API(c2_straight, SW_C2_STRAIGHT)
+F32_SWITCH_API(k24, SW_K24)
+F32_SWITCH_API(dh2_frag, SW_DH2_FRAG)
+F32_SWITCH_API(h1_frag, SW_H1_FRAG)
+F32_SWITCH_API(static_d0, SW_STATIC_D0)
+#undef F32_SWITCH_API
 
-// MYFYP_F32_FWD_FUSE: 1 (default) the owners accumulate the next step's forward inside C2 where that
-// loop is instantiated (layout 1, K split 1, no extra term), 0 the separate forward (A/B);
-// mlp_set_f32_fwd_fuse overrides it (tests; -1: back to the environment). mlp_f32_fwd_fuse_last: the
-// path the last layout-1/3 epoch launch took (1 fused, 0 separate, -1 none yet).
-static std::atomic<int> g_fuse_override{-1};
-static std::atomic<int> g_fuse_last{-1};
-static int f32_fwd_fuse_mode() {
-  const int o = g_fuse_override.load(std::memory_order_relaxed);
-  if (o >= 0) return o;
-  static const int v = [] {
-    const char* e = getenv("MYFYP_F32_FWD_FUSE");
-    return e != nullptr ? atoi(e) : 1;
-  }();
-  return v;
+// What one epoch launch takes, from its arguments and the switches. Layout 2 launches its own kernel: past
+// variant and dh2_frag the fields are those of layouts 1 / 3.
+struct F32Plan {
+  int variant = 1, KS = 1, ppl = 0;
+  size_t lds = 0;
+  bool rh = false, fuse = false, c2_straight = false, straight_all = false, k24 = false, dh2_frag = false, h1_frag = false, static_d0 = false;
+};
+static F32Plan f32_plan(const MLPArgs& a) {
+  auto on = [](int sw) { return g_sw[sw].mode() > 0; };
+  F32Plan pl;
+  pl.variant = f32_variant(a);
+  pl.dh2_frag = on(SW_DH2_FRAG) && pl.variant == 1;
+  if (pl.variant == 2) return pl;
+  pl.KS = f32_ks(a);
+  pl.rh = pl.variant == 3;
+  pl.ppl = ppl_of(pl.KS, pl.rh);
+  pl.lds = persistent_f32_lds_ks(a, pl.KS, pl.rh);
+  pl.fuse = on(SW_FWD_FUSE) && fuse_inst(pl.KS, pl.rh) && a.anchor == nullptr && a.cg == nullptr;
+  pl.c2_straight = on(SW_C2_STRAIGHT);
+  pl.straight_all = pl.c2_straight && !pl.rh && pl.KS == 1 && 7 + 8 * (rq_of(1) - 1) < ks1_of(a.D0);
+  pl.k24 = on(SW_K24) && pl.fuse && pl.straight_all && 8 * rq_of(1) < ks1_of(a.D0);
+  pl.h1_frag = on(SW_H1_FRAG) && pl.fuse && pl.dh2_frag;
+  pl.static_d0 = on(SW_STATIC_D0) && pl.h1_frag && pl.k24 && a.D0 == STATIC_D0;
+  return pl;
 }
-extern "C" int mlp_set_f32_fwd_fuse(int mode) { return g_fuse_override.exchange(mode < 0 ? -1 : mode); }
-extern "C" int mlp_f32_fwd_fuse_last() { return g_fuse_last.load(std::memory_order_relaxed); }
-
-// MYFYP_F32_C2_STRAIGHT: 1 (default) the owners of layout 1 at K split 1 run C2's straight-line body
-// in every wave whose register-resident K steps all exist, 0 the guarded body everywhere (A/B; same
-// bits either way); mlp_set_f32_c2_straight overrides it (tests; -1: back to the environment). The
-// switch reaches the kernel as pb.c2_straight. mlp_f32_c2_straight_last: what the last layout-1 epoch
-// launch could take: 1 if the switch was on and D0 gives every wave its K steps (K split 1, 24 K steps
-// or more: D0 >= 736), else 0 (-1: none yet).
-static std::atomic<int> g_straight_override{-1};
-static std::atomic<int> g_straight_last{-1};
-static int f32_c2_straight_mode() {
-  const int o = g_straight_override.load(std::memory_order_relaxed);
-  if (o >= 0) return o;
-  static const int v = [] {
-    const char* e = getenv("MYFYP_F32_C2_STRAIGHT");
-    return e != nullptr ? atoi(e) : 1;
-  }();
-  return v;
+// the instantiation a layout-1/3 plan launches for these arguments
+static const F32Row* f32_select(const F32Plan& pl, const MLPArgs& a) {
+  const bool extra = a.anchor != nullptr || a.cg != nullptr;
+  return f32_find(bp_of(a), a.opt.kind == 0, extra, pl.KS, pl.rh, pl.fuse, pl.k24, pl.h1_frag, pl.static_d0 ? STATIC_D0 : 0);
 }
-extern "C" int mlp_set_f32_c2_straight(int mode) { return g_straight_override.exchange(mode < 0 ? -1 : mode); }
-extern "C" int mlp_f32_c2_straight_last() { return g_straight_last.load(std::memory_order_relaxed); }
-
-// MYFYP_F32_K24: 1 (default) the wave that owns K step 24 (wave 0 of an owner, D0 >= 768) keeps that K
-// step's weights and moments in registers over the step loop and runs it inside C2's straight block,
-// 0 it stays LDS-resident in its guarded form (A/B; same bits either way); mlp_set_f32_k24 overrides
-// it (tests; -1: back to the environment). Values above 1 are taken as 1. It needs the fused forward
-// and the straight body; where it applies the launch sets pb.k24 and takes the K24 instantiation
-// (the mode as a kernel argument spilled: owner32). mlp_f32_k24_last: what the last
-// layout-1 epoch launch took: 1 if the switch, the fused forward and the straight body were on and
-// D0 has a K step 24, else 0 (-1: none yet).
-static std::atomic<int> g_k24_override{-1};
-static std::atomic<int> g_k24_last{-1};
-static int f32_k24_mode() {
-  const int o = g_k24_override.load(std::memory_order_relaxed);
-  if (o >= 0) return o;
-  static const int v = [] {
-    const char* e = getenv("MYFYP_F32_K24");
-    return e != nullptr ? atoi(e) : 1;
-  }();
-  return v;
-}
-extern "C" int mlp_set_f32_k24(int mode) { return g_k24_override.exchange(mode < 0 ? -1 : mode); }
-extern "C" int mlp_f32_k24_last() { return g_k24_last.load(std::memory_order_relaxed); }
-
-// MYFYP_F32_DH2_FRAG: 1 (default) the heads of layout 1 publish dH2 as the owners' MFMA A fragments
-// (dh2f[parity][hd][mt][lane], one 16-byte store per lane) and the owners' C1 loads them straight into
-// registers, 0 the [b][128] tile staged through LDS (A/B; same bits either way);
-// mlp_set_f32_dh2_frag overrides it (tests; -1: back to the environment). Values above 1 are taken as
-// 1. Heads and owners read it from the same launch argument, pb.dh2_frag. mlp_f32_dh2_frag_last: what
-// the last epoch launch took: 0 for layouts 2 and 3 and with the switch off (-1: none yet).
-static std::atomic<int> g_dh2_frag_override{-1};
-static std::atomic<int> g_dh2_frag_last{-1};
-static int f32_dh2_frag_mode() {
-  const int o = g_dh2_frag_override.load(std::memory_order_relaxed);
-  if (o >= 0) return o;
-  static const int v = [] {
-    const char* e = getenv("MYFYP_F32_DH2_FRAG");
-    return e != nullptr ? atoi(e) : 1;
-  }();
-  return v;
-}
-extern "C" int mlp_set_f32_dh2_frag(int mode) { return g_dh2_frag_override.exchange(mode < 0 ? -1 : mode); }
-extern "C" int mlp_f32_dh2_frag_last() { return g_dh2_frag_last.load(std::memory_order_relaxed); }
-
-// MYFYP_F32_H1_FRAG: 1 (default) the owners of layout 1 publish H1 as the heads' MFMA fragments
-// (h1f[parity][g][mt][lane], one 16-byte store per lane), the heads load them straight into registers
-// and accumulate H2 and dH2 transposed, 0 the [b][256] image staged through LDS and the row-major
-// accumulators (A/B; same bits either way); mlp_set_f32_h1_frag overrides it (tests; -1: back to the
-// environment). Values above 1 are taken as 1. A template argument of the kernel, not a launch
-// argument (head32's FRAG): it is taken only where the fused layout-1 K-split-1 kernels are launched
-// and dH2 goes as fragments too (MYFYP_F32_DH2_FRAG). mlp_f32_h1_frag_last: what the last epoch launch
-// took: 0 for layouts 2 and 3, K splits > 1, extra-term epochs, the separate forward and with either
-// switch off (-1: none yet).
-static std::atomic<int> g_h1_frag_override{-1};
-static std::atomic<int> g_h1_frag_last{-1};
-static int f32_h1_frag_mode() {
-  const int o = g_h1_frag_override.load(std::memory_order_relaxed);
-  if (o >= 0) return o;
-  static const int v = [] {
-    const char* e = getenv("MYFYP_F32_H1_FRAG");
-    return e != nullptr ? atoi(e) : 1;
-  }();
-  return v;
-}
-extern "C" int mlp_set_f32_h1_frag(int mode) { return g_h1_frag_override.exchange(mode < 0 ? -1 : mode); }
-extern "C" int mlp_f32_h1_frag_last() { return g_h1_frag_last.load(std::memory_order_relaxed); }
-
-// MYFYP_F32_STATIC_D0: 1 (default) an epoch of input width 784 (MNIST) that takes the K24 fragment
-// kernels runs the instantiation with that width as a compile-time constant (owner32's D0C: strides
-// as immediates, no column tests below K step 24, no multiplies), 0 the run-time-width kernel (A/B;
-// same bits either way); mlp_set_f32_static_d0 overrides it (tests; -1: back to the environment).
-// Values above 1 are taken as 1. Every other width takes the run-time kernel whatever the switch
-// says. mlp_f32_static_d0_last: what the last epoch launch took (-1: none yet).
-static std::atomic<int> g_static_d0_override{-1};
-static std::atomic<int> g_static_d0_last{-1};
-static int f32_static_d0_mode() {
-  const int o = g_static_d0_override.load(std::memory_order_relaxed);
-  if (o >= 0) return o;
-  static const int v = [] {
-    const char* e = getenv("MYFYP_F32_STATIC_D0");
-    return e != nullptr ? atoi(e) : 1;
-  }();
-  return v;
-}
-extern "C" int mlp_set_f32_static_d0(int mode) { return g_static_d0_override.exchange(mode < 0 ? -1 : mode); }
-extern "C" int mlp_f32_static_d0_last() { return g_static_d0_last.load(std::memory_order_relaxed); }
 
 hipError_t mlp_launch_persistent_f32_epoch(const MLPArgs& a, const MLPPersistF32Bufs& pb_in, hipStream_t s, bool zero_flags, const int* active) {
+  const F32Plan pl = f32_plan(a);
   MLPPersistF32Bufs pb = pb_in;
   pb.plain_ok = mlp_plain_pub_mode();
   pb.plain = 0;
-  pb.dh2_frag = f32_dh2_frag_mode() > 0 && f32_variant(a) == 1 ? 1 : 0;
-  g_dh2_frag_last.store(pb.dh2_frag, std::memory_order_relaxed);
+  pb.dh2_frag = pl.dh2_frag;
+  g_sw[SW_DH2_FRAG].report(pb.dh2_frag);
   if (zero_flags) {
     hipError_t e = hipMemsetAsync(pb.flags, 0, pb.flag_bytes, s);
     if (e != hipSuccess) return e;
   }
-  if (f32_variant(a) == 2) {
-    g_h1_frag_last.store(0, std::memory_order_relaxed);
-    g_static_d0_last.store(0, std::memory_order_relaxed);
+  if (pl.variant == 2) {
+    g_sw[SW_H1_FRAG].report(0);
+    g_sw[SW_STATIC_D0].report(0);
     mlp_f32v2_launch(a, pb, s);
     return hipGetLastError();
   }
-  const int KS = f32_ks(a);
-  const bool rh = f32_variant(a) == 3;
-  const int ppl = ppl_of(KS, rh);
-  const size_t lds = persistent_f32_lds_ks(a, KS, rh);
-  const bool fuse = f32_fwd_fuse_mode() != 0 && fuse_inst(KS, rh) && a.anchor == nullptr && a.cg == nullptr;
-  g_fuse_last.store(fuse ? 1 : 0, std::memory_order_relaxed);
-  pb.c2_straight = f32_c2_straight_mode() != 0 ? 1 : 0;
-  const bool straight_all = pb.c2_straight && !rh && KS == 1 && 7 + 8 * (rq_of(1) - 1) < ks1_of(a.D0);
-  g_straight_last.store(straight_all ? 1 : 0, std::memory_order_relaxed);
-  pb.k24 = f32_k24_mode() > 0 && fuse && straight_all && 8 * rq_of(1) < ks1_of(a.D0) ? 1 : 0;
-  g_k24_last.store(pb.k24, std::memory_order_relaxed);
-  const bool h1_frag = f32_h1_frag_mode() > 0 && fuse && pb.dh2_frag == 1;
-  g_h1_frag_last.store(h1_frag ? 1 : 0, std::memory_order_relaxed);
-  const bool static_d0 = f32_static_d0_mode() > 0 && h1_frag && pb.k24 == 1 && KS == 1 && !rh && a.D0 == STATIC_D0;
-  g_static_d0_last.store(static_d0 ? 1 : 0, std::memory_order_relaxed);
+  const F32Row* row = f32_select(pl, a);
+  if (row == nullptr) return hipErrorInvalidDeviceFunction;  // (no such instantiation: a missing kernel is an error)
+  pb.c2_straight = pl.c2_straight;
+  pb.k24 = row->K24;
+  g_sw[SW_FWD_FUSE].report(row->FUSE);
+  g_sw[SW_C2_STRAIGHT].report(pl.straight_all);
+  g_sw[SW_K24].report(row->K24);
+  g_sw[SW_H1_FRAG].report(row->FRAG);
+  g_sw[SW_STATIC_D0].report(row->D0C != 0);
   // groups of ppl peers: one launch each (a launch's gangs must all be co-resident), then the
   // recovery launches (attempt 1): a no-op exit for every gang that did not give up
   // (a group with no active peer is not launched: at one peer per device and K split 8 the other
@@ -2726,32 +2636,16 @@ hipError_t mlp_launch_persistent_f32_epoch(const MLPArgs& a, const MLPPersistF32
   // profiles/r6k_forced_trace)
   auto group_live = [&](int p0) {
     if (active == nullptr) return true;
-    for (int p = p0; p < p0 + ppl && p < a.P; ++p)
+    for (int p = p0; p < p0 + pl.ppl && p < a.P; ++p)
       if (active[p]) return true;
     return false;
   };
+  const dim3 grid(grid_of(pl.KS, pl.rh, pl.rh ? roles3_of(pl.KS, row->BP) : roles_of(pl.KS))), block(NT);
   for (int attempt = 0; attempt < 2; ++attempt)
-    for (int p0 = 0; p0 < a.P; p0 += ppl) {
+    for (int p0 = 0; p0 < a.P; p0 += pl.ppl) {
       if (!group_live(p0)) continue;
-      if (rh) {
-        if (KS == 2) {
-          if (a.Bpad == 64) launch_f32_bp<64, 2, true>(a, pb, s, p0, lds, attempt, fuse, h1_frag, static_d0);
-          else launch_f32_bp<32, 2, true>(a, pb, s, p0, lds, attempt, fuse, h1_frag, static_d0);
-        } else {
-          if (a.Bpad == 64) launch_f32_bp<64, 1, true>(a, pb, s, p0, lds, attempt, fuse, h1_frag, static_d0);
-          else launch_f32_bp<32, 1, true>(a, pb, s, p0, lds, attempt, fuse, h1_frag, static_d0);
-        }
-      } else if (KS == 8) {
-        launch_f32_bp<64, 8>(a, pb, s, p0, lds, attempt, fuse, h1_frag, static_d0);  // (f32_ks_wanted: Bpad 64 only)
-      } else if (KS == 4) {
-        launch_f32_bp<64, 4>(a, pb, s, p0, lds, attempt, fuse, h1_frag, static_d0);
-      } else if (KS == 2) {
-        if (a.Bpad == 64) launch_f32_bp<64, 2>(a, pb, s, p0, lds, attempt, fuse, h1_frag, static_d0);
-        else launch_f32_bp<32, 2>(a, pb, s, p0, lds, attempt, fuse, h1_frag, static_d0);
-      } else {
-        if (a.Bpad == 64) launch_f32_bp<64, 1>(a, pb, s, p0, lds, attempt, fuse, h1_frag, static_d0);
-        else launch_f32_bp<32, 1>(a, pb, s, p0, lds, attempt, fuse, h1_frag, static_d0);
-      }
+      void* args[] = {(void*)&a, &pb, &p0, &attempt};
+      (void)hipLaunchKernel(row->fn, grid, block, args, pl.lds, s);
     }
   return hipGetLastError();
 }

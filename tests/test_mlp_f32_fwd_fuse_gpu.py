@@ -8,90 +8,15 @@ gang packing), a few hundred samples each.
 """
 
 import ctypes
-import threading
 
 import pytest
-import torch
+
+from _mlp_f32_fit import _all, _assert_same, _pin_perms, _setup, dev, fp32_settings, lib  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
 
 ADAM = {"name": "adam", "lr": 1e-3}
 SGDM = {"name": "sgd", "lr": 1e-4, "momentum": 0.9}
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from myfyp_amd.ops import _native
-
-    return _native.load(required=True)
-
-
-@pytest.fixture(scope="module")
-def dev(lib):
-    return torch.device("cuda")
-
-
-@pytest.fixture(autouse=True)
-def fp32_settings(lib):
-    from myfyp_amd.parallel.mlp_engine import MLPGroup
-    from myfyp_amd.settings import Settings
-
-    old = (Settings.MLP_PRECISION, Settings.GANG_WINDOW, Settings.USE_FUSED_KERNELS)
-    Settings.MLP_PRECISION, Settings.GANG_WINDOW, Settings.USE_FUSED_KERNELS = "fp32", 5.0, True
-    MLPGroup.reset_all()
-    yield
-    lib.mlp_set_f32_fwd_fuse(-1)
-    MLPGroup.reset_all()
-    Settings.MLP_PRECISION, Settings.GANG_WINDOW, Settings.USE_FUSED_KERNELS = old
-
-
-def _setup(dev, P, B, per_peer, seed, spec):
-    """P peers of `per_peer` training samples each on layout 1 at owner K split 1 (the fused loop's
-    instantiations); SGD runs start from half-scale weights, as the other fp32 tests do."""
-    from myfyp_amd.learning.dataset.partition_strategies import RandomIIDPartitionStrategy
-    from myfyp_amd.learning.dataset.synthetic import synthetic_mnist
-    from myfyp_amd.learning.frameworks.torch import TorchLearner, TorchModel
-    from myfyp_amd.models import MLP
-
-    parts = synthetic_mnist(P * per_peer, 200, seed=seed).generate_partitions(P, RandomIIDPartitionStrategy)
-    learners = []
-    for i in range(P):
-        m = MLP(seed=50 + i)
-        if spec["name"] == "sgd":
-            with torch.no_grad():
-                for prm in m.parameters():
-                    prm.mul_(0.5)
-        m.optimizer_spec = lambda spec=spec: dict(spec)
-        learners.append(TorchLearner(TorchModel(m), parts[i], f"u{i}", batch_size=B))
-    assert all(l._engine is not None for l in learners), "fp32 engine not attached"
-    g = learners[0]._engine.group
-    assert g.precision == "fp32" and g.uses_persistent()
-    g.force_f32_ks = 1
-    g.force_f32_variant = 1
-    assert g.f32_ks() == 1 and g.f32_variant() == 1
-    n = [parts[i].get_num_samples() for i in range(P)]
-    assert n == [per_peer] * P, n
-    return learners, g, n
-
-
-def _pin_perms(dev, g, learners, n, seed=0):
-    def perm_fn(ep):
-        out = torch.zeros(g.capacity, g.nmax, dtype=torch.int32)
-        for i, l in enumerate(learners):
-            perm = torch.randperm(n[i], generator=torch.Generator().manual_seed(1000 * ep + 10 * seed + i))
-            out[l._engine.slot, : n[i]] = perm.to(torch.int32)
-        return out.to(dev)
-
-    g.perm_fn = perm_fn
-
-
-def _all(learners, what):
-    # every peer from its own thread: the group gangs the calls into one launch (a lone caller
-    # would wait out Settings.GANG_WINDOW for the others)
-    ts = [threading.Thread(target=getattr(l, what)) for l in learners]
-    [t.start() for t in ts]
-    [t.join() for t in ts]
-    torch.cuda.synchronize()
 
 
 def _run(lib, dev, fuse, P, B, per_peer, spec, epochs=2, seed=21, giveup=None):
@@ -101,7 +26,7 @@ def _run(lib, dev, fuse, P, B, per_peer, spec, epochs=2, seed=21, giveup=None):
 
     lib.mlp_set_f32_fwd_fuse(fuse)
     MLPGroup.reset_all()
-    learners, g, n = _setup(dev, P, B, per_peer, seed, spec)
+    learners, _, g, n = _setup(dev, P, B, per_peer, seed, spec)
     _pin_perms(dev, g, learners, n)
     for l in learners:
         l.set_epochs(epochs)
@@ -123,14 +48,6 @@ def _run(lib, dev, fuse, P, B, per_peer, spec, epochs=2, seed=21, giveup=None):
     if giveup is not None:
         g.debug_giveup(None)
     return out
-
-
-def _assert_same(a, b, adam):
-    for key in ("params", "m") + (("v",) if adam else ()):
-        for i, (x, y) in enumerate(zip(a[key], b[key])):
-            assert torch.isfinite(x).all(), f"peer {i} {key}: not finite"
-            assert torch.equal(x, y), f"peer {i} {key}: {int((x != y).sum())} elements differ, max {float((x - y).abs().max()):.3e}"
-    assert all(float(p.abs().max()) > 0 for p in a["params"])
 
 
 @pytest.mark.parametrize("per_peer", [300, 600])
