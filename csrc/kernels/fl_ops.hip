@@ -1,6 +1,8 @@
 // Federated-learning elementwise/reduction kernels (gfx950): FedAvg reductions, fused optimizers,
 // coordinate median, attack injection. All memory-bound: 16-byte vector accesses, grid-stride,
 // grid capped at 2048 blocks (cdna_hip_programming.md Guideline 11/13).
+#include <type_traits>
+#include <utility>
 #include "common.h"
 #include "fl_ops.h"
 
@@ -410,33 +412,29 @@ unsigned fl_krum_grid(int64_t n, int K) {
   return g > KRUM_MAX_GRID ? KRUM_MAX_GRID : g;
 }
 
+// The rows' coordinates 4g .. 4g+3 by one decision for all K rows, so that the K vector loads are
+// issued back to back (a branch per row, as load4<VEC> per row has, makes each load wait for the one
+// before). Which of the two forms a kernel uses was tuned per kernel.
 template <int K, bool VEC>
-__global__ __launch_bounds__(FL_BLOCK) void k_pairwise_sqdist(float* __restrict__ work, RowPtrs rows, int64_t n) {
-  constexpr int NP = K * (K - 1) / 2;
-  __shared__ float part[KRUM_WAVES][NP];
-  float acc[NP];
+__device__ __forceinline__ void load4_rows(float4 (&v)[K], const RowPtrs& rows, int64_t g, int64_t n) {
+  if (VEC && 4 * g + 4 <= n) {
 #pragma unroll
-  for (int q = 0; q < NP; ++q) acc[q] = 0.f;
-  const int64_t groups = (n + 3) / 4;
-  const int64_t stride = (int64_t)gridDim.x * FL_BLOCK;
-  for (int64_t g = (int64_t)blockIdx.x * FL_BLOCK + threadIdx.x; g < groups; g += stride) {
-    float4 v[K];
+    for (int k = 0; k < K; ++k) v[k] = reinterpret_cast<const float4*>(rows.p[k])[g];
+  } else {
 #pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = load4<VEC>(rows.p[k], g, n);
-    int q = 0;
-#pragma unroll
-    for (int i = 0; i < K; ++i) {
-#pragma unroll
-      for (int j = i + 1; j < K; ++j) {
-        const float dx = v[i].x - v[j].x, dy = v[i].y - v[j].y, dz = v[i].z - v[j].z, dw = v[i].w - v[j].w;
-        acc[q] += (dx * dx + dy * dy) + (dz * dz + dw * dw);
-        ++q;
-      }
-    }
+    for (int k = 0; k < K; ++k) v[k] = load4<false>(rows.p[k], g, n);
   }
-  // wave reduction (xor butterfly: a fixed order), then the block's waves through LDS in wave order
+}
+
+// A block's W per-thread partial sums to its slab slab[0 .. W): wave reduction (xor butterfly: a
+// fixed order), then the block's waves through LDS in wave order. Every block stores its whole slab
+// (zeros included): the one-block kernels sum every slab and the workspace is never cleared. Every
+// thread of the block calls it, once.
+template <int W>
+__device__ __forceinline__ void store_slab(float (&acc)[W], float* __restrict__ slab) {
+  __shared__ float part[KRUM_WAVES][W];
 #pragma unroll
-  for (int q = 0; q < NP; ++q) {
+  for (int q = 0; q < W; ++q) {
     float s = acc[q];
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
@@ -445,34 +443,67 @@ __global__ __launch_bounds__(FL_BLOCK) void k_pairwise_sqdist(float* __restrict_
   const int wave = threadIdx.x / 64;
   if ((threadIdx.x & 63) == 0) {
 #pragma unroll
-    for (int q = 0; q < NP; ++q) part[wave][q] = acc[q];
+    for (int q = 0; q < W; ++q) part[wave][q] = acc[q];
   }
   __syncthreads();
-  if (threadIdx.x < NP) {
+  if (threadIdx.x < W) {
     float s = part[0][threadIdx.x];
 #pragma unroll
     for (int w = 1; w < KRUM_WAVES; ++w) s += part[w][threadIdx.x];
-    work[(int64_t)blockIdx.x * NP + threadIdx.x] = s;  // every block stores its whole slab (zeros included)
+    slab[threadIdx.x] = s;
   }
 }
 
-// One block. Pair q of the slabs is (i, j), i < j, in the order k_pairwise_sqdist enumerates them.
-// The slabs are summed in double in a fixed two-level order: the block's threads split them into
-// C = KRUM_SELECT_BLOCK / NP chunks of consecutive slabs, each summed in slab order (eight loads in
-// flight), then the chunks in chunk order: the order depends on G and K only.
-// neighbours = min(max(1, K−f−2), K−1) smallest off-diagonal distances per row; the
-// max(1, min(m, K)) lowest scores are chosen, the lower index winning a tie; a NaN (a peer that
-// sent one) orders last, as numpy's sort does. coef[i] = w_i / Σ_chosen w, 0 for the others.
+// Group g of every row (load4<VEC> per row), then acc[q] += Σ over the four coordinates of
+// (x_i − x_j)², pair q = (i, j), i < j, i ascending and then j. The one loop body of
+// k_pairwise_sqdist and k_dnc_sqdist: their slabs agree bit for bit.
+// Which of d·d + d·d becomes a fused multiply-add is the compiler's choice under the default
+// -ffp-contract, per instantiation: that the VEC and the scalar form of a kernel round alike rests on
+// it making the same choice in both. tests/test_robust_dispatch_gpu.py compares the two forms at
+// every K and is what guards it.
+template <int K, bool VEC>
+__device__ __forceinline__ void pair_sqdist_add(const RowPtrs& rows, int64_t g, int64_t n, float (&acc)[K * (K - 1) / 2]) {
+  float4 v[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) v[k] = load4<VEC>(rows.p[k], g, n);
+  int q = 0;
+#pragma unroll
+  for (int i = 0; i < K; ++i) {
+#pragma unroll
+    for (int j = i + 1; j < K; ++j) {
+      const float dx = v[i].x - v[j].x, dy = v[i].y - v[j].y, dz = v[i].z - v[j].z, dw = v[i].w - v[j].w;
+      acc[q] += (dx * dx + dy * dy) + (dz * dz + dw * dw);
+      ++q;
+    }
+  }
+}
+
+template <int K, bool VEC>
+__global__ __launch_bounds__(FL_BLOCK) void k_pairwise_sqdist(float* __restrict__ work, RowPtrs rows, int64_t n) {
+  constexpr int NP = K * (K - 1) / 2;
+  float acc[NP];
+#pragma unroll
+  for (int q = 0; q < NP; ++q) acc[q] = 0.f;
+  const int64_t groups = (n + 3) / 4;
+  const int64_t stride = (int64_t)gridDim.x * FL_BLOCK;
+  for (int64_t g = (int64_t)blockIdx.x * FL_BLOCK + threadIdx.x; g < groups; g += stride) {
+    pair_sqdist_add<K, VEC>(rows, g, n, acc);
+  }
+  store_slab<NP>(acc, work + (int64_t)blockIdx.x * NP);
+}
+
+// The slab sum of every one-block kernel below: column t of work[G][W] for thread t < W (0 for the
+// others), in double, in a fixed two-level order: the block's threads split the slabs into
+// C = KRUM_SELECT_BLOCK / W chunks of consecutive slabs, each summed in slab order (eight loads in
+// flight), then the chunks in chunk order. The order depends on G and W only, so every rank sums the
+// identical gathered buffer to the identical bits and selects the same peers. W <= 120 (at least 8
+// chunks); W == 0 sums nothing. One barrier inside; every thread of the block calls it.
 #define KRUM_SELECT_BLOCK 1024
-// The slab sum of the one-block selection kernels (Krum, Bulyan): d[i][j] <- pair (i, j)'s sum in
-// the order above, 0 on the diagonal. Ends with a barrier; every thread of the block calls it.
-__device__ __forceinline__ void krum_sum_slabs(const float* __restrict__ work, int G, int K, double (*d)[16], double* part) {
+__device__ __forceinline__ double sum_slabs(const float* __restrict__ work, int G, int W, double* part) {
   const int t = threadIdx.x;
-  const int NP = K * (K - 1) / 2;
-  if (t < 256) (&d[0][0])[t] = 0.0;
-  const int C = NP > 0 ? KRUM_SELECT_BLOCK / NP : 0;  // NP <= 120: at least 8 chunks
-  if (t < C * NP) {
-    const int p = t % NP, c = t / NP;
+  const int C = W > 0 ? KRUM_SELECT_BLOCK / W : 0;
+  if (t < C * W) {
+    const int p = t % W, c = t / W;
     const int per = (G + C - 1) / C;
     const int g1 = min(G, (c + 1) * per);
     int g = c * per;
@@ -480,17 +511,29 @@ __device__ __forceinline__ void krum_sum_slabs(const float* __restrict__ work, i
     for (; g + 8 <= g1; g += 8) {
       float v[8];
 #pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = work[(int64_t)(g + u) * NP + p];
+      for (int u = 0; u < 8; ++u) v[u] = work[(int64_t)(g + u) * W + p];
 #pragma unroll
       for (int u = 0; u < 8; ++u) s += (double)v[u];
     }
-    for (; g < g1; ++g) s += (double)work[(int64_t)g * NP + p];
-    part[c * NP + p] = s;
+    for (; g < g1; ++g) s += (double)work[(int64_t)g * W + p];
+    part[c * W + p] = s;
   }
   __syncthreads();
+  double s = 0.0;
+  if (t < W)
+    for (int c = 0; c < C; ++c) s += part[c * W + t];
+  return s;
+}
+
+// The pair slabs of k_pairwise_sqdist summed (sum_slabs, W = K(K-1)/2) into d[i][j] = d[j][i], pair q
+// being (i, j), i < j, in the order k_pairwise_sqdist enumerates them; 0 on the diagonal. Ends with a
+// barrier; every thread of the block calls it.
+__device__ __forceinline__ void krum_sum_slabs(const float* __restrict__ work, int G, int K, double (*d)[16], double* part) {
+  const int t = threadIdx.x;
+  const int NP = K * (K - 1) / 2;
+  if (t < 256) (&d[0][0])[t] = 0.0;
+  const double s = sum_slabs(work, G, NP, part);
   if (t < NP) {
-    double s = 0.0;
-    for (int c = 0; c < C; ++c) s += part[c * NP + t];
     int i = 0, rem = t;
     while (rem >= K - 1 - i) {
       rem -= K - 1 - i;
@@ -524,6 +567,10 @@ __device__ __forceinline__ double krum_row_score(double (*d)[16], int t, int K, 
   return s;
 }
 
+// One block: the distances by krum_sum_slabs, then per row the
+// neighbours = min(max(1, K−f−2), K−1) smallest off-diagonal distances; the
+// max(1, min(m, K)) lowest scores are chosen, the lower index winning a tie; a NaN (a peer that
+// sent one) orders last, as numpy's sort does. coef[i] = w_i / Σ_chosen w, 0 for the others.
 __global__ __launch_bounds__(KRUM_SELECT_BLOCK) void k_krum_select(const float* __restrict__ work, int G, int K, int f, int m, RowW w,
                                                                    double* __restrict__ dist, double* __restrict__ score, float* __restrict__ coef) {
   __shared__ double d[16][16];
@@ -797,7 +844,7 @@ __global__ __launch_bounds__(FL_BLOCK) void k_bulyan_mean(OutPtrs outs, int P, R
     float4 x[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) x[k] = {inf, inf, inf, inf};
-    // one decision for all K rows (see k_gm_dist); on[k] is uniform over the grid
+    // one decision for all K rows (see load4_rows); on[k] is uniform over the grid
     if (VEC && 4 * g + 4 <= n) {
 #pragma unroll
       for (int k = 0; k < K; ++k)
@@ -850,7 +897,6 @@ __global__ __launch_bounds__(FL_BLOCK) void k_bulyan_mean(OutPtrs outs, int P, R
 // the screen pass.
 template <int K, bool VEC>
 __global__ __launch_bounds__(FL_BLOCK) void k_gm_dist(float* __restrict__ work, RowPtrs rows, const float* __restrict__ coef, int64_t n) {
-  __shared__ float part[KRUM_WAVES][K];
   float c[K], acc[K];
   int r = -1;
 #pragma unroll
@@ -863,15 +909,7 @@ __global__ __launch_bounds__(FL_BLOCK) void k_gm_dist(float* __restrict__ work, 
   const int64_t stride = (int64_t)gridDim.x * FL_BLOCK;
   for (int64_t g = (int64_t)blockIdx.x * FL_BLOCK + threadIdx.x; g < groups; g += stride) {
     float4 v[K];
-    // one decision for all K rows, so that the K vector loads are issued back to back (a branch
-    // per row makes each load wait for the one before)
-    if (VEC && 4 * g + 4 <= n) {
-#pragma unroll
-      for (int k = 0; k < K; ++k) v[k] = reinterpret_cast<const float4*>(rows.p[k])[g];
-    } else {
-#pragma unroll
-      for (int k = 0; k < K; ++k) v[k] = load4<false>(rows.p[k], g, n);
-    }
+    load4_rows<K, VEC>(v, rows, g, n);
     // the reference row by a wave-uniform predicated copy: v[] stays in registers
     float4 xr = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -890,31 +928,11 @@ __global__ __launch_bounds__(FL_BLOCK) void k_gm_dist(float* __restrict__ work, 
       acc[k] += (dx * dx + dy * dy) + (dz * dz + dw * dw);
     }
   }
-  // wave reduction (xor butterfly: a fixed order), then the block's waves through LDS in wave order
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    float s = acc[k];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
-    acc[k] = s;
-  }
-  const int wave = threadIdx.x / 64;
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) part[wave][k] = acc[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < K) {
-    float s = part[0][threadIdx.x];
-#pragma unroll
-    for (int w = 1; w < KRUM_WAVES; ++w) s += part[w][threadIdx.x];
-    work[(int64_t)blockIdx.x * K + threadIdx.x] = s;  // every block stores its whole slab
-  }
+  store_slab<K>(acc, work + (int64_t)blockIdx.x * K);
 }
 
-// One block. The slabs work[G][K] are summed in double in k_krum_select's fixed two-level order
-// (C = KRUM_SELECT_BLOCK / K chunks of consecutive slabs, then the chunks in chunk order); thread 0
-// then runs the K-term arithmetic in double, k ascending. what[K] holds ŵ: the sample weights with
+// One block. The slabs work[G][K] are summed by sum_slabs; thread 0 then runs the K-term arithmetic
+// in double, k ascending. what[K] holds ŵ: the sample weights with
 // 0 for a rejected row (all 1 where every valid weight is 0), written by the screen call and read
 // by the iterations. No valid row: ŵ = 0 and coef = w / Σw (or 1/K), which every iteration keeps
 // (Σβ = 0), so the output is the plain mean and shows the NaN; dist is NaN then.
@@ -926,29 +944,8 @@ __global__ __launch_bounds__(KRUM_SELECT_BLOCK) void k_gm_reweight(const float* 
   __shared__ double part[KRUM_SELECT_BLOCK];
   __shared__ double sum[16], d[16], beta[16];
   const int tid = threadIdx.x;
-  const int C = KRUM_SELECT_BLOCK / K;  // K <= 16: at least 64 chunks
-  if (tid < C * K) {
-    const int p = tid % K, c = tid / K;
-    const int per = (G + C - 1) / C;
-    const int g1 = min(G, (c + 1) * per);
-    int g = c * per;
-    double s = 0.0;
-    for (; g + 8 <= g1; g += 8) {
-      float v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = work[(int64_t)(g + u) * K + p];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) s += (double)v[u];
-    }
-    for (; g < g1; ++g) s += (double)work[(int64_t)g * K + p];
-    part[c * K + p] = s;
-  }
-  __syncthreads();
-  if (tid < K) {
-    double s = 0.0;
-    for (int c = 0; c < C; ++c) s += part[c * K + tid];
-    sum[tid] = s;
-  }
+  const double colsum = sum_slabs(work, G, K, part);
+  if (tid < K) sum[tid] = colsum;
   __syncthreads();
   if (tid != 0) return;
   if (mode == GM_SCREEN) {
@@ -1044,7 +1041,6 @@ __device__ __forceinline__ void collude_coord(float (&e)[K], float& delta, float
 template <int K, bool VEC>
 __global__ __launch_bounds__(FL_BLOCK) void k_collude_stats(float* __restrict__ work, RowPtrs rows, int64_t n) {
   constexpr int W = 2 * K + 1;
-  __shared__ float part[KRUM_WAVES][W];
   float acc[W];
 #pragma unroll
   for (int q = 0; q < W; ++q) acc[q] = 0.f;
@@ -1052,14 +1048,7 @@ __global__ __launch_bounds__(FL_BLOCK) void k_collude_stats(float* __restrict__ 
   const int64_t stride = (int64_t)gridDim.x * FL_BLOCK;
   for (int64_t g = (int64_t)blockIdx.x * FL_BLOCK + threadIdx.x; g < groups; g += stride) {
     float4 v[K];
-    // one decision for all K rows (see k_gm_dist)
-    if (VEC && 4 * g + 4 <= n) {
-#pragma unroll
-      for (int k = 0; k < K; ++k) v[k] = reinterpret_cast<const float4*>(rows.p[k])[g];
-    } else {
-#pragma unroll
-      for (int k = 0; k < K; ++k) v[k] = load4<false>(rows.p[k], g, n);
-    }
+    load4_rows<K, VEC>(v, rows, g, n);
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       float e[K], delta, sigma;
@@ -1074,31 +1063,11 @@ __global__ __launch_bounds__(FL_BLOCK) void k_collude_stats(float* __restrict__ 
       acc[2 * K] = fmaf(sigma, sigma, acc[2 * K]);
     }
   }
-  // wave reduction (xor butterfly: a fixed order), then the block's waves through LDS in wave order
-#pragma unroll
-  for (int q = 0; q < W; ++q) {
-    float s = acc[q];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
-    acc[q] = s;
-  }
-  const int wave = threadIdx.x / 64;
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int q = 0; q < W; ++q) part[wave][q] = acc[q];
-  }
-  __syncthreads();
-  if (threadIdx.x < W) {
-    float s = part[0][threadIdx.x];
-#pragma unroll
-    for (int w = 1; w < KRUM_WAVES; ++w) s += part[w][threadIdx.x];
-    work[(int64_t)blockIdx.x * W + threadIdx.x] = s;  // every block stores its whole slab
-  }
+  store_slab<W>(acc, work + (int64_t)blockIdx.x * W);
 }
 
-// One block. The pair slabs pairs[Gp][K(K-1)/2] go through krum_sum_slabs; the stats slabs
-// stats[G][2K+1] are summed in the same fixed two-level order (C = KRUM_SELECT_BLOCK / (2K+1) chunks
-// of consecutive slabs, then the chunks in chunk order). Thread 0 then works in double:
+// One block. The pair slabs pairs[Gp][K(K-1)/2] go through krum_sum_slabs, the stats slabs
+// stats[G][2K+1] through sum_slabs. Thread 0 then works in double:
 //   D = max_ij d_ij, S = max_i Σ_j d_ij (j ascending)
 //   min-max: the largest γ >= 0 with max_i |m − x_i|² <= D, m = μ − γσ. |m − x_i|² = a_i − 2γ b_i + γ² s,
 //            so γ = min_i (b_i + sqrt(max(0, b_i² + s (D − a_i)))) / s, i ascending
@@ -1117,29 +1086,8 @@ __global__ __launch_bounds__(KRUM_SELECT_BLOCK) void k_collude_solve(const float
   const int tid = threadIdx.x;
   krum_sum_slabs(pairs, Gp, K, d, part);
   const int W = 2 * K + 1;
-  const int C = KRUM_SELECT_BLOCK / W;  // W <= 33: at least 31 chunks
-  if (tid < C * W) {
-    const int p = tid % W, c = tid / W;
-    const int per = (G + C - 1) / C;
-    const int g1 = min(G, (c + 1) * per);
-    int g = c * per;
-    double s = 0.0;
-    for (; g + 8 <= g1; g += 8) {
-      float v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = stats[(int64_t)(g + u) * W + p];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) s += (double)v[u];
-    }
-    for (; g < g1; ++g) s += (double)stats[(int64_t)g * W + p];
-    part[c * W + p] = s;
-  }
-  __syncthreads();
-  if (tid < W) {
-    double s = 0.0;
-    for (int c = 0; c < C; ++c) s += part[c * W + tid];
-    sum[tid] = s;
-  }
+  const double colsum = sum_slabs(stats, G, W, part);
+  if (tid < W) sum[tid] = colsum;
   __syncthreads();
   if (tid != 0) return;
   double D = 0.0, S = 0.0;
@@ -1190,6 +1138,7 @@ __global__ __launch_bounds__(FL_BLOCK) void k_collude_write(OutPtrs outs, int P,
   for (int64_t g = (int64_t)blockIdx.x * FL_BLOCK + threadIdx.x; g < groups; g += stride) {
     float4 v[K];
     float4 r4 = {0.f, 0.f, 0.f, 0.f};
+    // load4_rows with the reference row inside the same decision
     if (VEC && 4 * g + 4 <= n) {
 #pragma unroll
       for (int k = 0; k < K; ++k) v[k] = reinterpret_cast<const float4*>(rows.p[k])[g];
@@ -1304,15 +1253,14 @@ __global__ __launch_bounds__(FL_BLOCK) void k_scale_add_noise(float* __restrict_
 // splitmix64(key[t] ^ τ) < thr or τ == forced[t] (the host derives key, thr and forced from the
 // seed and the round); all != 0 takes every tile and hashes nothing.
 
-// Same body and accumulation order as k_pairwise_sqdist<K, VEC>: with every tile taken, block b of
-// iteration t stores the slab k_pairwise_sqdist's block b stores, bit for bit. g >> 6 is the same
+// k_pairwise_sqdist<K, VEC>'s row loads, pair_sqdist_add and store_slab: with every tile taken, block
+// b of iteration t stores the slab k_pairwise_sqdist's block b stores, bit for bit. g >> 6 is the same
 // in all lanes of a wave (FL_BLOCK and the grid stride are multiples of 64): it goes through
 // readfirstlane, so the hash is scalar work and the skip a scalar branch. Every register index is
 // static.
 template <int K, bool VEC>
 __global__ __launch_bounds__(FL_BLOCK) void k_dnc_sqdist(float* __restrict__ work, RowPtrs rows, DncTiles tiles, int64_t n) {
   constexpr int NP = K * (K - 1) / 2;
-  __shared__ float part[KRUM_WAVES][NP];
   float acc[NP];
 #pragma unroll
   for (int q = 0; q < NP; ++q) acc[q] = 0.f;
@@ -1327,39 +1275,9 @@ __global__ __launch_bounds__(FL_BLOCK) void k_dnc_sqdist(float* __restrict__ wor
                            (uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(tg & 0xFFFFFFFFll));
       if (!(splitmix64(key ^ tau) < tiles.thr || tau == forced)) continue;
     }
-    float4 v[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = load4<VEC>(rows.p[k], g, n);
-    int q = 0;
-#pragma unroll
-    for (int i = 0; i < K; ++i) {
-#pragma unroll
-      for (int j = i + 1; j < K; ++j) {
-        const float dx = v[i].x - v[j].x, dy = v[i].y - v[j].y, dz = v[i].z - v[j].z, dw = v[i].w - v[j].w;
-        acc[q] += (dx * dx + dy * dy) + (dz * dz + dw * dw);
-        ++q;
-      }
-    }
+    pair_sqdist_add<K, VEC>(rows, g, n, acc);
   }
-#pragma unroll
-  for (int q = 0; q < NP; ++q) {
-    float s = acc[q];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
-    acc[q] = s;
-  }
-  const int wave = threadIdx.x / 64;
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int q = 0; q < NP; ++q) part[wave][q] = acc[q];
-  }
-  __syncthreads();
-  if (threadIdx.x < NP) {
-    float s = part[0][threadIdx.x];
-#pragma unroll
-    for (int w = 1; w < KRUM_WAVES; ++w) s += part[w][threadIdx.x];
-    work[((int64_t)it * gridDim.x + blockIdx.x) * NP + threadIdx.x] = s;
-  }
+  store_slab<NP>(acc, work + ((int64_t)it * gridDim.x + blockIdx.x) * NP);
 }
 
 // One block. Per iteration it (slabs work[it][G][K(K-1)/2], summed by krum_sum_slabs into D):
@@ -1544,27 +1462,35 @@ void fl_broadcast_rows(float* stacked, const float* src, int P, int64_t n, int64
   if (gx > 256) gx = 256;
   hipLaunchKernelGGL(k_broadcast_rows, dim3(gx, P), dim3(FL_BLOCK), 0, s, stacked, src, P, n, ld, mask, vec_ok(ld, stacked, src));
 }
+
+// The robust aggregators' kernels take the row count (and Bulyan's f) as template arguments.
+// dispatch_int calls f(std::integral_constant<int, x>) for the run-time x in LO..HI and returns true;
+// for an x outside the range it calls nothing, so nothing is launched, and returns false.
+// dispatch_rows does so for a row count K in LO..16 and hands f the alignment flag as a second
+// compile-time argument (std::bool_constant<vec>).
+template <int LO, typename F, int... I>
+static bool dispatch_seq(int x, F& f, std::integer_sequence<int, I...>) {
+  return ((x == LO + I ? (f(std::integral_constant<int, LO + I>{}), true) : false) || ...);
+}
+template <int LO, int HI, typename F>
+static bool dispatch_int(int x, F f) {
+  return dispatch_seq<LO>(x, f, std::make_integer_sequence<int, HI - LO + 1>{});
+}
+template <int LO, typename F>
+static bool dispatch_rows(int K, bool vec, F f) {
+  return dispatch_int<LO, 16>(K, [&](auto k) {
+    if (vec) f(k, std::true_type{});
+    else f(k, std::false_type{});
+  });
+}
+
 void fl_coordinate_median(const OutPtrs& outs, int P, const RowPtrs& rows, int K, int64_t n, hipStream_t s) {
   const dim3 g(grid_for(n)), b(FL_BLOCK);
-  switch (K) {
-#define MED_CASE(KK) \
-  case KK: hipLaunchKernelGGL(k_coordinate_median<KK>, g, b, 0, s, outs, P, rows, n); break;
-    MED_CASE(1) MED_CASE(2) MED_CASE(3) MED_CASE(4) MED_CASE(5) MED_CASE(6) MED_CASE(7) MED_CASE(8)
-    MED_CASE(9) MED_CASE(10) MED_CASE(11) MED_CASE(12) MED_CASE(13) MED_CASE(14) MED_CASE(15) MED_CASE(16)
-#undef MED_CASE
-    default: break;
-  }
+  dispatch_int<1, 16>(K, [&](auto k) { hipLaunchKernelGGL(k_coordinate_median<k()>, g, b, 0, s, outs, P, rows, n); });
 }
 void fl_trimmed_mean(const OutPtrs& outs, int P, const RowPtrs& rows, int K, int trim, int64_t n, hipStream_t s) {
   const dim3 g(grid_for(n)), b(FL_BLOCK);
-  switch (K) {
-#define TRIM_CASE(KK) \
-  case KK: hipLaunchKernelGGL(k_trimmed_mean<KK>, g, b, 0, s, outs, P, rows, trim, n); break;
-    TRIM_CASE(1) TRIM_CASE(2) TRIM_CASE(3) TRIM_CASE(4) TRIM_CASE(5) TRIM_CASE(6) TRIM_CASE(7) TRIM_CASE(8)
-    TRIM_CASE(9) TRIM_CASE(10) TRIM_CASE(11) TRIM_CASE(12) TRIM_CASE(13) TRIM_CASE(14) TRIM_CASE(15) TRIM_CASE(16)
-#undef TRIM_CASE
-    default: break;
-  }
+  dispatch_int<1, 16>(K, [&](auto k) { hipLaunchKernelGGL(k_trimmed_mean<k()>, g, b, 0, s, outs, P, rows, trim, n); });
 }
 static bool all_aligned16(const RowPtrs& rows, int K, const OutPtrs* outs, int P) {
   uintptr_t bits = 0;
@@ -1577,17 +1503,8 @@ static unsigned launch_pairwise_sqdist(float* work, const RowPtrs& rows, int K, 
   const unsigned grid = K > 1 ? fl_krum_grid(n, K) : 0;
   const bool vec = all_aligned16(rows, K, nullptr, 0);
   const dim3 g(grid), b(FL_BLOCK);
-  switch (K) {
-#define DIST_CASE(KK)                                                                           \
-  case KK:                                                                                      \
-    if (vec) hipLaunchKernelGGL((k_pairwise_sqdist<KK, true>), g, b, 0, s, work, rows, n);      \
-    else hipLaunchKernelGGL((k_pairwise_sqdist<KK, false>), g, b, 0, s, work, rows, n);         \
-    break;
-    DIST_CASE(2) DIST_CASE(3) DIST_CASE(4) DIST_CASE(5) DIST_CASE(6) DIST_CASE(7) DIST_CASE(8)
-    DIST_CASE(9) DIST_CASE(10) DIST_CASE(11) DIST_CASE(12) DIST_CASE(13) DIST_CASE(14) DIST_CASE(15) DIST_CASE(16)
-#undef DIST_CASE
-    default: break;  // K == 1: no pair, nothing to measure
-  }
+  // from 2: K == 1 has no pair, nothing to measure
+  dispatch_rows<2>(K, vec, [&](auto k, auto v) { hipLaunchKernelGGL((k_pairwise_sqdist<k(), v()>), g, b, 0, s, work, rows, n); });
   return grid;
 }
 void fl_krum_select(float* work, const RowPtrs& rows, const RowW& w, int K, int f, int m, int64_t n, double* dist, double* score, float* coef,
@@ -1598,17 +1515,7 @@ void fl_krum_select(float* work, const RowPtrs& rows, const RowW& w, int K, int 
 void fl_coef_mean(const OutPtrs& outs, int P, const RowPtrs& rows, int K, const float* coef, int64_t n, hipStream_t s) {
   const bool vec = all_aligned16(rows, K, &outs, P);
   const dim3 g(grid_for((n + 3) / 4)), b(FL_BLOCK);
-  switch (K) {
-#define COEF_CASE(KK)                                                                           \
-  case KK:                                                                                      \
-    if (vec) hipLaunchKernelGGL((k_coef_mean<KK, true>), g, b, 0, s, outs, P, rows, coef, n);   \
-    else hipLaunchKernelGGL((k_coef_mean<KK, false>), g, b, 0, s, outs, P, rows, coef, n);      \
-    break;
-    COEF_CASE(1) COEF_CASE(2) COEF_CASE(3) COEF_CASE(4) COEF_CASE(5) COEF_CASE(6) COEF_CASE(7) COEF_CASE(8)
-    COEF_CASE(9) COEF_CASE(10) COEF_CASE(11) COEF_CASE(12) COEF_CASE(13) COEF_CASE(14) COEF_CASE(15) COEF_CASE(16)
-#undef COEF_CASE
-    default: break;
-  }
+  dispatch_rows<1>(K, vec, [&](auto k, auto v) { hipLaunchKernelGGL((k_coef_mean<k(), v()>), g, b, 0, s, outs, P, rows, coef, n); });
 }
 void fl_clipped_gossip(float* work, const OutPtrs& rows, int K, const ClipPlan& plan, int64_t n, double* dist, double* tau, float* w_eff,
                        hipStream_t s) {
@@ -1619,45 +1526,20 @@ void fl_clipped_gossip(float* work, const OutPtrs& rows, int K, const ClipPlan& 
   hipLaunchKernelGGL(k_clip_plan, dim3(1), dim3(KRUM_SELECT_BLOCK), 0, s, work, (int)grid, K, plan, dist, tau, w_eff);
   const bool vec = all_aligned16(src, K, nullptr, 0);
   const dim3 g(grid_for((n + 3) / 4)), b(FL_BLOCK);
-  switch (K) {
-#define CLIP_CASE(KK)                                                                  \
-  case KK:                                                                             \
-    if (vec) hipLaunchKernelGGL((k_clipped_mix<KK, true>), g, b, 0, s, rows, w_eff, n); \
-    else hipLaunchKernelGGL((k_clipped_mix<KK, false>), g, b, 0, s, rows, w_eff, n);    \
-    break;
-    CLIP_CASE(2) CLIP_CASE(3) CLIP_CASE(4) CLIP_CASE(5) CLIP_CASE(6) CLIP_CASE(7) CLIP_CASE(8)
-    CLIP_CASE(9) CLIP_CASE(10) CLIP_CASE(11) CLIP_CASE(12) CLIP_CASE(13) CLIP_CASE(14) CLIP_CASE(15) CLIP_CASE(16)
-#undef CLIP_CASE
-    default: break;
-  }
-}
-// k_bulyan_mean<K, F>: F runs over the attacker bounds K admits (K >= 4F + 3, or F == 0)
-template <int K, int F>
-static void bulyan_mean_launch(bool vec, dim3 g, const OutPtrs& outs, int P, const RowPtrs& rows, const float* coef, int64_t n, hipStream_t s) {
-  if (vec) hipLaunchKernelGGL((k_bulyan_mean<K, F, true>), g, dim3(FL_BLOCK), 0, s, outs, P, rows, coef, n);
-  else hipLaunchKernelGGL((k_bulyan_mean<K, F, false>), g, dim3(FL_BLOCK), 0, s, outs, P, rows, coef, n);
-}
-template <int K>
-static void bulyan_mean_f(int f, bool vec, dim3 g, const OutPtrs& outs, int P, const RowPtrs& rows, const float* coef, int64_t n, hipStream_t s) {
-  if (f == 0) bulyan_mean_launch<K, 0>(vec, g, outs, P, rows, coef, n, s);
-  if constexpr (K >= 7)
-    if (f == 1) bulyan_mean_launch<K, 1>(vec, g, outs, P, rows, coef, n, s);
-  if constexpr (K >= 11)
-    if (f == 2) bulyan_mean_launch<K, 2>(vec, g, outs, P, rows, coef, n, s);
-  if constexpr (K >= 15)
-    if (f == 3) bulyan_mean_launch<K, 3>(vec, g, outs, P, rows, coef, n, s);
+  dispatch_rows<2>(K, vec, [&](auto k, auto v) { hipLaunchKernelGGL((k_clipped_mix<k(), v()>), g, b, 0, s, rows, w_eff, n); });
 }
 void fl_bulyan_mean(const OutPtrs& outs, int P, const RowPtrs& rows, int K, int f, const float* coef, int64_t n, hipStream_t s) {
   const bool vec = all_aligned16(rows, K, &outs, P);
-  const dim3 g(grid_for((n + 3) / 4));
-  switch (K) {
-#define BUL_CASE(KK) \
-  case KK: bulyan_mean_f<KK>(f, vec, g, outs, P, rows, coef, n, s); break;
-    BUL_CASE(1) BUL_CASE(2) BUL_CASE(3) BUL_CASE(4) BUL_CASE(5) BUL_CASE(6) BUL_CASE(7) BUL_CASE(8)
-    BUL_CASE(9) BUL_CASE(10) BUL_CASE(11) BUL_CASE(12) BUL_CASE(13) BUL_CASE(14) BUL_CASE(15) BUL_CASE(16)
-#undef BUL_CASE
-    default: break;
-  }
+  const dim3 g(grid_for((n + 3) / 4)), b(FL_BLOCK);
+  dispatch_rows<1>(K, vec, [&](auto k, auto v) {
+    constexpr int KK = decltype(k)::value;
+    constexpr bool VEC = decltype(v)::value;
+    dispatch_int<0, 3>(f, [&](auto ff) {
+      // k_bulyan_mean<K, F> exists for the attacker bounds K admits only (K >= 4F + 3, or F == 0)
+      constexpr int F = decltype(ff)::value;
+      if constexpr (F == 0 || KK >= 4 * F + 3) hipLaunchKernelGGL((k_bulyan_mean<KK, F, VEC>), g, b, 0, s, outs, P, rows, coef, n);
+    });
+  });
 }
 void fl_bulyan(float* work, const OutPtrs& outs, int P, const RowPtrs& rows, int K, int f, int64_t n, double* dist, double* score, int* pick,
                float* coef, hipStream_t s) {
@@ -1672,17 +1554,7 @@ void fl_dnc(float* work, const OutPtrs& outs, int P, const RowPtrs& rows, const 
     const unsigned grid = fl_krum_grid(n, K);
     const bool vec = all_aligned16(rows, K, nullptr, 0);
     const dim3 g(grid, iters), b(FL_BLOCK);
-    switch (K) {
-#define DNC_CASE(KK)                                                                            \
-  case KK:                                                                                      \
-    if (vec) hipLaunchKernelGGL((k_dnc_sqdist<KK, true>), g, b, 0, s, work, rows, tiles, n);    \
-    else hipLaunchKernelGGL((k_dnc_sqdist<KK, false>), g, b, 0, s, work, rows, tiles, n);       \
-    break;
-      DNC_CASE(2) DNC_CASE(3) DNC_CASE(4) DNC_CASE(5) DNC_CASE(6) DNC_CASE(7) DNC_CASE(8)
-      DNC_CASE(9) DNC_CASE(10) DNC_CASE(11) DNC_CASE(12) DNC_CASE(13) DNC_CASE(14) DNC_CASE(15) DNC_CASE(16)
-#undef DNC_CASE
-      default: return;
-    }
+    dispatch_rows<2>(K, vec, [&](auto k, auto v) { hipLaunchKernelGGL((k_dnc_sqdist<k(), v()>), g, b, 0, s, work, rows, tiles, n); });
     hipLaunchKernelGGL(k_dnc_select, dim3(1), dim3(KRUM_SELECT_BLOCK), 0, s, work, (int)grid, K, m, iters, w, dist, score, lam, removed, coef);
   }
   if (P > 0) fl_coef_mean(outs, P, rows, K, coef, n, s);
@@ -1696,17 +1568,7 @@ void fl_geometric_median(float* work, const RowPtrs& rows, const RowW& w, int K,
   // pass -1 is the screen (coefficients 0: the sums are |x_k|^2), passes 0..iters-1 the iterations
   for (int t = -1; t < iters; ++t) {
     const float* c = t < 0 ? nullptr : coef;
-    switch (K) {
-#define GM_CASE(KK)                                                                     \
-  case KK:                                                                              \
-    if (vec) hipLaunchKernelGGL((k_gm_dist<KK, true>), g, b, 0, s, work, rows, c, n);   \
-    else hipLaunchKernelGGL((k_gm_dist<KK, false>), g, b, 0, s, work, rows, c, n);      \
-    break;
-      GM_CASE(1) GM_CASE(2) GM_CASE(3) GM_CASE(4) GM_CASE(5) GM_CASE(6) GM_CASE(7) GM_CASE(8)
-      GM_CASE(9) GM_CASE(10) GM_CASE(11) GM_CASE(12) GM_CASE(13) GM_CASE(14) GM_CASE(15) GM_CASE(16)
-#undef GM_CASE
-      default: return;
-    }
+    if (!dispatch_rows<1>(K, vec, [&](auto k, auto v) { hipLaunchKernelGGL((k_gm_dist<k(), v()>), g, b, 0, s, work, rows, c, n); })) return;
     hipLaunchKernelGGL(k_gm_reweight, dim3(1), dim3(KRUM_SELECT_BLOCK), 0, s, work, (int)grid, K, t < 0 ? GM_SCREEN : GM_ITERATE, t < 0 ? 0 : t, w, nu,
                        what, coef, dist, obj);
   }
@@ -1720,17 +1582,7 @@ void fl_collude(float* work, const OutPtrs& outs, int P, const RowPtrs& rows, in
     float* stats = work + (int64_t)grid * (K * (K - 1) / 2);
     const bool vec = all_aligned16(rows, K, nullptr, 0);
     const dim3 g(grid), b(FL_BLOCK);
-    switch (K) {
-#define CST_CASE(KK)                                                                      \
-  case KK:                                                                                \
-    if (vec) hipLaunchKernelGGL((k_collude_stats<KK, true>), g, b, 0, s, stats, rows, n); \
-    else hipLaunchKernelGGL((k_collude_stats<KK, false>), g, b, 0, s, stats, rows, n);    \
-    break;
-      CST_CASE(1) CST_CASE(2) CST_CASE(3) CST_CASE(4) CST_CASE(5) CST_CASE(6) CST_CASE(7) CST_CASE(8)
-      CST_CASE(9) CST_CASE(10) CST_CASE(11) CST_CASE(12) CST_CASE(13) CST_CASE(14) CST_CASE(15) CST_CASE(16)
-#undef CST_CASE
-      default: return;
-    }
+    if (!dispatch_rows<1>(K, vec, [&](auto k, auto v) { hipLaunchKernelGGL((k_collude_stats<k(), v()>), g, b, 0, s, stats, rows, n); })) return;
     hipLaunchKernelGGL(k_collude_solve, dim3(1), dim3(KRUM_SELECT_BLOCK), 0, s, work, (int)gp, stats, (int)grid, K, kind, gamma, stat);
   }
   const bool vec = all_aligned16(rows, K, &outs, P) && (reinterpret_cast<uintptr_t>(ref) & 15u) == 0;
@@ -1738,17 +1590,9 @@ void fl_collude(float* work, const OutPtrs& outs, int P, const RowPtrs& rows, in
   float* gout = solve ? nullptr : gamma;
   const float gval = kind == COLLUDE_ALIE ? -cb : -ca;
   const dim3 g(grid_for((n + 3) / 4)), b(FL_BLOCK);
-  switch (K) {
-#define CWR_CASE(KK)                                                                                                         \
-  case KK:                                                                                                                   \
-    if (vec) hipLaunchKernelGGL((k_collude_write<KK, true>), g, b, 0, s, outs, P, rows, ref, ca, cb, cr, gin, gout, gval, n); \
-    else hipLaunchKernelGGL((k_collude_write<KK, false>), g, b, 0, s, outs, P, rows, ref, ca, cb, cr, gin, gout, gval, n);    \
-    break;
-    CWR_CASE(1) CWR_CASE(2) CWR_CASE(3) CWR_CASE(4) CWR_CASE(5) CWR_CASE(6) CWR_CASE(7) CWR_CASE(8)
-    CWR_CASE(9) CWR_CASE(10) CWR_CASE(11) CWR_CASE(12) CWR_CASE(13) CWR_CASE(14) CWR_CASE(15) CWR_CASE(16)
-#undef CWR_CASE
-    default: break;
-  }
+  dispatch_rows<1>(K, vec, [&](auto k, auto v) {
+    hipLaunchKernelGGL((k_collude_write<k(), v()>), g, b, 0, s, outs, P, rows, ref, ca, cb, cr, gin, gout, gval, n);
+  });
 }
 void fl_scaffold_reduce(float* buf, const RowPtrs& dy, const RowPtrs& dc, const RowW& w, int K, int64_t n, hipStream_t s) {
   hipLaunchKernelGGL(k_scaffold_reduce, dim3(grid_for(n)), dim3(FL_BLOCK), 0, s, buf, dy, dc, w, K, n);

@@ -985,12 +985,25 @@ static bool rows_ok(int k, const char* what) {
   g_last_error = std::string(what) + " supports 1..16 rows";
   return false;
 }
+static RowPtrs row_ptrs(const uint64_t* srcs, int K) {
+  RowPtrs rows{};
+  for (int k = 0; k < K; ++k) rows.p[k] = reinterpret_cast<const float*>(srcs[k]);
+  return rows;
+}
+static OutPtrs out_ptrs(const uint64_t* outs, int P) {
+  OutPtrs o{};
+  for (int p = 0; p < P; ++p) o.p[p] = reinterpret_cast<float*>(outs[p]);
+  return o;
+}
+static RowW row_weights(const float* w, int K) {
+  RowW ww{};
+  for (int k = 0; k < K; ++k) ww.w[k] = w[k];
+  return ww;
+}
 int myfyp_coordinate_median_multi(const uint64_t* outs, int P, const uint64_t* srcs, int K, int64_t n, void* stream) {
   if (!rows_ok(K, "coordinate_median") || !rows_ok(P, "coordinate_median outputs")) return 2;
-  RowPtrs rows{};
-  OutPtrs o{};
-  for (int k = 0; k < K; ++k) rows.p[k] = reinterpret_cast<const float*>(srcs[k]);
-  for (int p = 0; p < P; ++p) o.p[p] = reinterpret_cast<float*>(outs[p]);
+  const RowPtrs rows = row_ptrs(srcs, K);
+  const OutPtrs o = out_ptrs(outs, P);
   fl_coordinate_median(o, P, rows, K, n, (hipStream_t)stream);
   CHECK_HIP(hipGetLastError());
   return 0;
@@ -1004,10 +1017,8 @@ int myfyp_trimmed_mean_multi(const uint64_t* outs, int P, const uint64_t* srcs, 
     g_last_error = "trimmed_mean: n >= 1 and 0 <= 2*trim < K";
     return 2;
   }
-  RowPtrs rows{};
-  OutPtrs o{};
-  for (int k = 0; k < K; ++k) rows.p[k] = reinterpret_cast<const float*>(srcs[k]);
-  for (int p = 0; p < P; ++p) o.p[p] = reinterpret_cast<float*>(outs[p]);
+  const RowPtrs rows = row_ptrs(srcs, K);
+  const OutPtrs o = out_ptrs(outs, P);
   fl_trimmed_mean(o, P, rows, K, trim, n, (hipStream_t)stream);
   CHECK_HIP(hipGetLastError());
   return 0;
@@ -1024,14 +1035,9 @@ int myfyp_krum_multi(const uint64_t* outs, int P, const uint64_t* srcs, const fl
     g_last_error = "krum: n >= 1 and the work / dist / score / coef buffers are required";
     return 2;
   }
-  RowPtrs rows{};
-  OutPtrs o{};
-  RowW ww{};
-  for (int k = 0; k < K; ++k) {
-    rows.p[k] = reinterpret_cast<const float*>(srcs[k]);
-    ww.w[k] = w[k];
-  }
-  for (int p = 0; p < P; ++p) o.p[p] = reinterpret_cast<float*>(outs[p]);
+  const RowPtrs rows = row_ptrs(srcs, K);
+  const OutPtrs o = out_ptrs(outs, P);
+  const RowW ww = row_weights(w, K);
   fl_krum_select(work, rows, ww, K, f, m, n, dist, score, coef, (hipStream_t)stream);
   CHECK_HIP(hipGetLastError());
   if (P > 0) {
@@ -1057,9 +1063,8 @@ int myfyp_clipped_gossip(const uint64_t* rows, int K, const float* W_host, int m
     return 2;
   }
   ClipPlan plan{};
-  OutPtrs r{};
+  const OutPtrs r = out_ptrs(rows, K);
   for (int p = 0; p < K; ++p) {
-    r.p[p] = reinterpret_cast<float*>(rows[p]);
     for (int q = 0; q < K; ++q) {
       const float wq = W_host[p * K + q];
       if (!(wq >= 0.f) || wq - wq != 0.f) {
@@ -1099,10 +1104,8 @@ int myfyp_bulyan_multi(const uint64_t* outs, int P, const uint64_t* srcs, int K,
     g_last_error = "bulyan: the row tables and the work / dist / score / pick / coef buffers are required";
     return 2;
   }
-  RowPtrs rows{};
-  OutPtrs o{};
-  for (int k = 0; k < K; ++k) rows.p[k] = reinterpret_cast<const float*>(srcs[k]);
-  for (int p = 0; p < P; ++p) o.p[p] = reinterpret_cast<float*>(outs[p]);
+  const RowPtrs rows = row_ptrs(srcs, K);
+  const OutPtrs o = out_ptrs(outs, P);
   fl_bulyan(work, o, P, rows, K, f, n, dist, score, pick, coef, (hipStream_t)stream);
   CHECK_HIP(hipGetLastError());
   return 0;
@@ -1115,10 +1118,8 @@ int myfyp_bulyan_mean_multi(const uint64_t* outs, int P, const uint64_t* srcs, i
     g_last_error = "bulyan_mean: at least one output, the row tables and coef are required";
     return 2;
   }
-  RowPtrs rows{};
-  OutPtrs o{};
-  for (int k = 0; k < K; ++k) rows.p[k] = reinterpret_cast<const float*>(srcs[k]);
-  for (int p = 0; p < P; ++p) o.p[p] = reinterpret_cast<float*>(outs[p]);
+  const RowPtrs rows = row_ptrs(srcs, K);
+  const OutPtrs o = out_ptrs(outs, P);
   fl_bulyan_mean(o, P, rows, K, f, coef, n, (hipStream_t)stream);
   CHECK_HIP(hipGetLastError());
   return 0;
@@ -1149,15 +1150,10 @@ int myfyp_dnc_multi(const uint64_t* outs, int P, const uint64_t* srcs, const flo
     g_last_error = "dnc: a subsample needs the keys and the forced tiles";
     return 2;
   }
-  RowPtrs rows{};
-  OutPtrs o{};
-  RowW ww{};
+  const RowPtrs rows = row_ptrs(srcs, K);
+  const OutPtrs o = out_ptrs(outs, P);
+  const RowW ww = row_weights(w_host, K);
   DncTiles tiles{};
-  for (int k = 0; k < K; ++k) {
-    rows.p[k] = reinterpret_cast<const float*>(srcs[k]);
-    ww.w[k] = w_host[k];
-  }
-  for (int p = 0; p < P; ++p) o.p[p] = reinterpret_cast<float*>(outs[p]);
   for (int t = 0; t < iters && !all_tiles; ++t) {
     tiles.key[t] = keys_host[t];
     tiles.forced[t] = forced_host[t];
@@ -1184,18 +1180,15 @@ int myfyp_geomed_multi(const uint64_t* outs, int P, const uint64_t* srcs, const 
     g_last_error = "geometric_median: n >= 1 and the work / coef / dist / obj buffers are required";
     return 2;
   }
-  RowPtrs rows{};
-  OutPtrs o{};
-  RowW ww{};
   for (int k = 0; k < K; ++k) {
     if (!(w[k] >= 0.f) || w[k] - w[k] != 0.f) {
       g_last_error = "geometric_median: weights are finite and >= 0";
       return 2;
     }
-    rows.p[k] = reinterpret_cast<const float*>(srcs[k]);
-    ww.w[k] = w[k];
   }
-  for (int p = 0; p < P; ++p) o.p[p] = reinterpret_cast<float*>(outs[p]);
+  const RowPtrs rows = row_ptrs(srcs, K);
+  const OutPtrs o = out_ptrs(outs, P);
+  const RowW ww = row_weights(w, K);
   fl_geometric_median(work, rows, ww, K, iters, nu, n, coef, dist, obj, (hipStream_t)stream);
   CHECK_HIP(hipGetLastError());
   if (P > 0) {
@@ -1225,10 +1218,8 @@ int myfyp_collude_multi(const uint64_t* outs, int P, const uint64_t* srcs, int K
     g_last_error = "collude: n >= 1 and the row tables and the work / gamma / stat buffers are required";
     return 2;
   }
-  RowPtrs rows{};
-  OutPtrs o{};
-  for (int k = 0; k < K; ++k) rows.p[k] = reinterpret_cast<const float*>(srcs[k]);
-  for (int p = 0; p < P; ++p) o.p[p] = reinterpret_cast<float*>(outs[p]);
+  const RowPtrs rows = row_ptrs(srcs, K);
+  const OutPtrs o = out_ptrs(outs, P);
   fl_collude(work, o, P, rows, K, kind, ca, cb, cr, ref, n, gamma, stat, (hipStream_t)stream);
   CHECK_HIP(hipGetLastError());
   return 0;
@@ -1238,22 +1229,13 @@ int myfyp_scaffold_reduce(float* buf, const uint64_t* dy, const uint64_t* dc, co
     g_last_error = "scaffold_reduce supports 0..16 rows";
     return 2;
   }
-  RowPtrs y{}, c{};
-  RowW ww{};
-  for (int k = 0; k < K; ++k) {
-    y.p[k] = reinterpret_cast<const float*>(dy[k]);
-    c.p[k] = reinterpret_cast<const float*>(dc[k]);
-    ww.w[k] = w[k];
-  }
-  fl_scaffold_reduce(buf, y, c, ww, K, n, (hipStream_t)stream);
+  fl_scaffold_reduce(buf, row_ptrs(dy, K), row_ptrs(dc, K), row_weights(w, K), K, n, (hipStream_t)stream);
   CHECK_HIP(hipGetLastError());
   return 0;
 }
 int myfyp_scaffold_apply(const uint64_t* outs, int P, const float* x_start, const float* buf, float* c, int c_init, float glr, int64_t n, void* stream) {
   if (!rows_ok(P, "scaffold_apply outputs")) return 2;
-  OutPtrs o{};
-  for (int p = 0; p < P; ++p) o.p[p] = reinterpret_cast<float*>(outs[p]);
-  fl_scaffold_apply(o, P, x_start, buf, c, c_init, glr, n, (hipStream_t)stream);
+  fl_scaffold_apply(out_ptrs(outs, P), P, x_start, buf, c, c_init, glr, n, (hipStream_t)stream);
   CHECK_HIP(hipGetLastError());
   return 0;
 }
